@@ -31,6 +31,14 @@ under profiles/), measured HBM traffic against both peaks and against a compulso
 8(d) algorithmic-bytes figure as a throughput, not a fraction -- and ``cpu_baseline``: the C oracle (a port:
 the reference has no CPU tracer) on a bounded sample of the same rays on the host cores, with the full
 gradient parity of that sample next to it.
+
+A plain run does only what the headline figure needs: set-up, the warm-up steps, the ``--steps`` timed steps and the
+JSON line (``ms_per_step`` = wall time of one timed step).  Everything else it measures or checks -- the repeated frame,
+the triangulation timings, ``roofline``, ``cpu_baseline`` and, on the default line, ``other_workloads`` -- runs only
+with ``--full``.  ``--dump-outputs DIR`` writes what the last timed step returned to its caller (forward outputs and
+gradients, or the rendered frame) as ``DIR/<name>.npy``, float32 (float64 for integer outputs); an output too large for
+the 60 MB budget is written as a fixed, seeded sample of its rows (rays or points).  With the same arguments the inputs
+are the same in every run, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -148,6 +156,12 @@ def parse_args(argv=None):
                     help="Pipeline.forward_mode (experiments): 1 blocks, 2 eager, 3 = --strict-scan, 4 persistent waves with refill, "
                          "5 eager behind the block-level LDS cell table (auto for sorted flat batches)")
     ap.add_argument("--grad-pitch", default=None, help="Pipeline.gradient_row_pitch: auto (default), dense, or floats")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed extras: repeated frame, triangulation timings, roofline, cpu_baseline and, "
+                         "on the default line, other_workloads (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, 60 MB at most: "
+                         "larger outputs as a fixed, seeded sample of their rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--repeat-frame", action="store_true",
                     help="time the steps on ONE frame / batch traced over and over (what rounds 1-4 reported) instead of on "
@@ -283,6 +297,37 @@ def load_counters(workload_name, custom):
     return entry
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs writes at most this much in all
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: ``arrays`` = [(name, tensor or ndarray, number of leading dims that index rays / points)], written
+    as ``directory/<name>.npy``: floating outputs as float32 (float64 stays float64), integer outputs as float64 (exact).
+    The budget is shared out smallest output first; an output larger than its share keeps a sample of its rows, drawn
+    with a fixed seed from the row count alone, in ascending order -- the same rows in every run of the same arguments."""
+    os.makedirs(directory, exist_ok=True)
+    host = []
+    for name, a, lead in arrays:
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        if a.dtype.kind == "f":
+            a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        else:
+            a = a.astype(np.float64)
+        host.append((name, a, lead))
+    left, todo = DUMP_BUDGET_BYTES, len(host)
+    for name, a, lead in sorted(host, key=lambda x: x[1].nbytes):
+        share = left // todo
+        if a.nbytes > share:
+            rows = a.reshape((int(np.prod(a.shape[:lead], dtype=np.int64)),) + a.shape[lead:])
+            row_bytes = max(rows.nbytes // max(rows.shape[0], 1), 1)
+            keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows.shape[0], share // row_bytes,
+                                                                         replace=False))
+            a = rows[keep]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+        left, todo = left - a.nbytes, todo - 1
+
+
 # ------------------------------------------------------------------------------------------------
 
 
@@ -324,10 +369,11 @@ def main():
     W = resolve_workload(args)
     result = run_train_loop(args, W, env) if W["kind"] == "loop" else run_workload(args, W, env)
     if result is not None and on_gpu and world == 1 and args.workload == "north-star" and not W.get("custom") and \
-            not args.forward_only and not args.quantiles and not args.no_other_workloads and not args.no_cpu_baseline:
-        # the driver runs this file once, with no flags -- so that one run also observes the other
-        # BASELINE configurations (untimed extras of the north-star line; each is what `--workload <name>` prints,
-        # with fewer steps and a smaller CPU sample, reduced to the figures a reader checks first)
+            args.full and not args.forward_only and not args.quantiles and not args.no_other_workloads and \
+            not args.no_cpu_baseline:
+        # one --full run also observes the other BASELINE configurations (untimed extras of the
+        # north-star line; each is what `--workload <name> --full` prints, with fewer steps and a smaller CPU sample,
+        # reduced to the figures a reader checks first)
         result["other_workloads"] = other_workloads(args, env)
     if result is not None:
         print(json.dumps(result), flush=True)
@@ -359,8 +405,12 @@ def run_train_loop(args, W, env):
                                   triangulate=gpu_triangulation)
     if world > 1 and rank == 0:
         dist.barrier()
+    kept = {}
     its, detail = train_loop.run(args, env, fm, sh_degree=W["sh"], iterations=args.steps, rays_per_batch=W["rays"],
-                                 width=W["width"], height=W["height"], densify_at=max(1, args.steps // 2))
+                                 width=W["width"], height=W["height"], densify_at=max(1, args.steps // 2), keep=kept)
+    if args.dump_outputs and rank == 0:     # what the loop hands its caller: the trained scene
+        m = kept.pop("model")
+        dump_outputs(args.dump_outputs, [(k, getattr(m, k), 1) for k in ("primal_points", "density", "att_dc", "att_sh")])
     if world > 1:           # the slowest rank's clock (the ranks meet in every step's exchange: they agree to a step)
         t = torch.tensor([detail["wall_seconds"]], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -407,6 +457,7 @@ def other_workloads(args, env):
         sub = argparse.Namespace(**vars(args))
         sub.workload, sub.steps, sub.warmup = name, 5, 3
         sub.cpu_seconds = min(args.cpu_seconds, 6.0)
+        sub.dump_outputs = None     # the outputs written are the north-star line's own
         t0 = time.time()
         try:
             r = run_workload(sub, resolve_workload(sub), env)
@@ -656,6 +707,16 @@ def run_workload(args, W, env):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        if W["kind"] == "render":
+            dumped = [("rgba8", render_out, 2)]
+        else:
+            lead = last["out"]["rgba"].dim() - 1      # leading dims that index rays
+            dumped = [(k, last["out"][k], lead) for k in ("rgba", "num_intersections", "depth", "depth_indices")
+                      if k in last["out"]]
+            if last["res"] is not None:     # (ray_grad is returned zero-filled: nothing to compare)
+                dumped += [(k, last["res"][k], 1) for k in ("points_grad", "attr_grad")]
+        dump_outputs(args.dump_outputs, dumped)
 
     mean_ms = lambda evs: float(np.mean([a.elapsed_time(b) for a, b in evs])) if (evs and on_gpu) else 0.0
     fwd_ms, bwd_ms, pack_ms, exch_ms = mean_ms(fwd_ev), mean_ms(bwd_ev), mean_ms(pack_ev), mean_ms(exch_ev)
@@ -672,7 +733,7 @@ def run_workload(args, W, env):
     # the value.  A repeated frame takes its forward's block order from its own previous trace.  Also leaves view 0's
     # outputs in `last` for the extras and checks below.
     repeated = None
-    if fresh and on_gpu and not args.no_repeated_frame:
+    if args.full and fresh and on_gpu and not args.no_repeated_frame:
         timed_fwd, timed_bwd, timed_pack = list(fwd_ev), list(bwd_ev), list(pack_ev)
         del fwd_ev[:], bwd_ev[:], pack_ev[:], exch_ev[:]
         for _ in range(2):
@@ -686,7 +747,7 @@ def run_workload(args, W, env):
         repeated = {"ms_per_step": round(rep * 1e3, 4), "forward_ms": round(mean_ms(fwd_ev), 4),
                     "backward_ms": round(mean_ms(bwd_ev), 4)}
         fwd_ev[:], bwd_ev[:], pack_ev[:] = timed_fwd, timed_bwd, timed_pack
-    elif fresh:
+    elif args.full and fresh:
         step(False, view0)
         sync()
 
@@ -729,7 +790,7 @@ def run_workload(args, W, env):
             detail["exchange_rows_per_rank"] = tracer.sparse.last_counts
             detail["exchange_bytes_in_per_rank"] = int((world - 1) * max(tracer.sparse.last_counts) * pitch * 4)
             detail["dense_allreduce_bytes_per_rank"] = int(2 * (world - 1) / world * points.shape[0] * (3 + A) * 4)
-    if on_gpu and world == 1 and args.workload == "north-star" and not W.get("custom"):
+    if args.full and on_gpu and world == 1 and args.workload == "north-star" and not W.get("custom"):
         # what train.py:243-248 does between steps: the triangulation follows the points.  Untimed extra, beside the
         # metric: the foam's own lists rebuilt on the GPU from scratch (and compared with the lists the frame was traced
         # through: Qhull's, when they came from the cache), then an incremental rebuild after a 3 %-of-the-spacing move.
@@ -761,7 +822,7 @@ def run_workload(args, W, env):
         }
         del tree, tree2, t_adj, t_off, m_adj, m_off, moved
     roofline = None
-    if on_gpu and rank == 0:
+    if args.full and on_gpu and rank == 0:
         my_rays = tracer._shard(rays) if strong else rays
         my_start = tracer._shard(start) if strong else start
         is_render = W["kind"] == "render"
@@ -858,7 +919,7 @@ def run_workload(args, W, env):
         result["data"] = "synthetic (launcher self-test on CPU tensors through " + test_factory + ": not a measurement)"
 
     # ---- CPU baseline: the oracle on a bounded sample of the same rays --------------------------
-    if on_gpu and not args.no_cpu_baseline and world == 1:
+    if args.full and on_gpu and not args.no_cpu_baseline and world == 1:
         try:
             if W["kind"] == "render":
                 result["cpu_baseline"] = cpu_baseline_render(W, fm, cam, start_np, render_out, args.strict_scan)

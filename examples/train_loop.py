@@ -198,8 +198,9 @@ def _check_replicas(rdist, model):
 
 
 def run(args, env, fm, sh_degree=3, iterations=300, rays_per_batch=1_000_000, cameras=8, width=1920, height=1080,
-        densify_at=150, densify_factor=1.15, quantile_weight=1e-4, white_background=True):
-    """The loop; returns (iterations per second, detail dict)."""
+        densify_at=150, densify_factor=1.15, quantile_weight=1e-4, white_background=True, keep=None):
+    """The loop; returns (iterations per second, detail dict).  ``keep``: a dict that receives the trained scene as
+    ``keep["model"]`` (bench.py --dump-outputs)."""
     import gc
 
     import radfoam
@@ -373,4 +374,6 @@ def run(args, env, fm, sh_degree=3, iterations=300, rays_per_batch=1_000_000, ca
         },
         "ms_per_call": {k: round(sec.ms[k] / sec.calls[k], 3) for k in sec.ms},
     }
+    if keep is not None:
+        keep["model"] = model
     return iterations / wall, detail

@@ -14,22 +14,22 @@ if has tests; then
   (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2) > $O/smoke.log; tail -1 $O/smoke.log
 fi
 if has bench; then
-  # the driver's line: north-star + the untimed other_workloads record (c2, c5, render, train-batch)
-  (timeout 1500 python bench.py --steps 20 --warmup 5 2>$O/bench.err | tail -1) > $O/bench.json
+  # the north-star line with every extra (--full): roofline, CPU baseline, other_workloads (c2, c5, render, train-batch)
+  (timeout 1500 python bench.py --full --steps 20 --warmup 5 2>$O/bench.err | tail -1) > $O/bench.json
   # the launcher paths with one GPU: bench.py's own (--gpus 1 needs none) and the driver's torch.distributed.run
   (timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-other-workloads 2>/dev/null | tail -1) > $O/bench_torchrun1.json
 fi
 if has configs; then
   for w in c2 c5 train-batch train-batch-lit render; do
-    (timeout 900 python bench.py --workload $w --steps 10 --warmup 3 2>$O/bench_$w.err | tail -1) > $O/bench_$w.json
+    (timeout 900 python bench.py --full --workload $w --steps 10 --warmup 3 2>$O/bench_$w.err | tail -1) > $O/bench_$w.json
   done
-  (timeout 600 python bench.py --forward-only --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1) > $O/bench_ns_fwd.json
+  (timeout 600 python bench.py --full --forward-only --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1) > $O/bench_ns_fwd.json
   # the training loop's call pattern (train.py:176-180): two depth quantiles per ray with depth gradients
-  (timeout 900 python bench.py --quantiles 2 --steps 10 --warmup 3 2>$O/bench_ns_q2.err | tail -1) > $O/bench_ns_q2.json
-  (timeout 900 python bench.py --workload train-batch --quantiles 2 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1) > $O/bench_train-batch_q2.json
-  (timeout 900 python bench.py --workload train-batch --sh-degree 2 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1) > $O/bench_train-batch_sh2.json
+  (timeout 900 python bench.py --full --quantiles 2 --steps 10 --warmup 3 2>$O/bench_ns_q2.err | tail -1) > $O/bench_ns_q2.json
+  (timeout 900 python bench.py --full --workload train-batch --quantiles 2 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1) > $O/bench_train-batch_q2.json
+  (timeout 900 python bench.py --full --workload train-batch --sh-degree 2 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1) > $O/bench_train-batch_sh2.json
   # every segment lit (what the scene's softplus gives: real training), the reference's quotient scan, and the loop itself
-  (timeout 900 python bench.py --strict-scan --steps 10 --warmup 3 2>$O/bench_ns_strict.err | tail -1) > $O/bench_ns_strict.json
+  (timeout 900 python bench.py --full --strict-scan --steps 10 --warmup 3 2>$O/bench_ns_strict.err | tail -1) > $O/bench_ns_strict.json
   (timeout 900 python bench.py --workload train-loop 2>$O/bench_train-loop.err | tail -1) > $O/bench_train-loop.json
   [ -x scripts/probe/global_atomics ] && (timeout 120 scripts/probe/global_atomics > $O/probe_global_atomics.log 2>&1)
 fi
