@@ -89,7 +89,7 @@ def test_forward_flat_rays_quantiles_contribution(foam_factory, d, forward_mode)
     assert abs(float(got["contribution"].double().sum()) - float(got["rgba"][..., 3].double().sum())) < 1e-2
 
 
-@pytest.mark.parametrize("forward_mode", [1, 2, 5])
+@pytest.mark.parametrize("forward_mode", [1, 2, 3, 4, 5])
 @pytest.mark.parametrize("d", [0, 1, 2, 3])
 def test_forward_half_attributes(foam_factory, d, forward_mode):
     fm = foam_factory(6000, d, 13)

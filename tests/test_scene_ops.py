@@ -307,3 +307,68 @@ def test_batch_fetcher_on_the_device_follows_the_references_index_sequence(shuff
         for b in range(2):
             got = torch.cat([p.next() for p in parts])
             assert got.shape[0] == bs and torch.equal(got, whole.next()), (world, b)
+
+
+def _cast_accumulator_vector():
+    """fp32 values around every place a float -> half conversion can go wrong, then random bit patterns."""
+    f = lambda *v: np.array(v, dtype=np.float32)
+    nxt = lambda x, to: np.nextafter(np.float32(x), np.float32(to))
+    around = lambda x: [nxt(x, 0.0), np.float32(x), nxt(x, np.inf)]
+    edge = []
+    for x in (2.0 ** -25, 2.0 ** -24, 2.0 ** -14, 65504.0, 65520.0):      # half of the least subnormal (a tie to 0), the
+        edge += around(x)                                                 # least subnormal, the least normal, max, overflow
+    edge += [1.5 * 2.0 ** -24, 2.5 * 2.0 ** -24, 1023.5 * 2.0 ** -24]     # subnormal ties: to even (up), to even (down), up
+    # mantissa ties at 1.0: 1 + 2^-11 is half way between 1 and 1 + 2^-10 (to even: down), 1 + 3 * 2^-11 rounds up to even
+    for x in (1.0 + 2.0 ** -11, 1.0 + 3.0 * 2.0 ** -11, 2047.0 * 2.0 ** -10 + 2.0 ** -11):
+        edge += around(x)
+    edge += [65519.996, 65536.0, 1e5, 3e38, np.inf, np.nan, 0.0]
+    edge = f(*edge)
+    special = np.concatenate([edge, -edge])
+    rng = np.random.default_rng(11)
+    bits = rng.integers(0, 2 ** 32, size=100_003 - special.size, dtype=np.uint64).astype(np.uint32)
+    bits[:20000] = (bits[:20000] & np.uint32(0x807FFFFF)) | (rng.integers(98, 146, 20000).astype(np.uint32) << 23)  # the half range
+    return np.concatenate([special, bits.view(np.float32)])
+
+
+@pytest.mark.gpu
+def test_cast_accumulator_rounds_like_ieee():
+    """rf_cast_accumulator (the single rounding of an fp16 caller's fp32 accumulators, used by the C++ binding): fp32 ->
+    fp16 equals numpy's astype(float16) -- round to nearest even, subnormals, overflow to inf at 65520, signed zeros --
+    bit for bit (NaN for NaN) at counts around the 256-thread block; fp32 -> fp32 copies the bits; count 0 writes
+    nothing; an unknown attribute type is an error."""
+    import ctypes as C
+    from radfoam_amd import _lib
+
+    lib = _lib.load()
+    src = _cast_accumulator_vector()
+    assert src.size == 100_003 and np.isnan(src).sum() >= 2 and np.signbit(src[src == 0]).any()
+    with np.errstate(over="ignore", invalid="ignore"):
+        want = src.astype(np.float16)
+    assert np.isinf(want[np.isfinite(src)]).any() and (want[src != 0] == 0).any()     # overflow and underflow are in
+    sub = (want != 0) & (np.abs(want.astype(np.float32)) < 2.0 ** -14)
+    assert sub.sum() > 100
+    dsrc = torch.from_numpy(src).cuda()
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for count in (1, 255, 256, 257, 100_003):
+        for start in (0, src.size - count):                      # the special values lead, the random ones trail
+            for attr_type, np_t, torch_t in ((_lib.RF_ATTR_FLOAT16, np.uint16, torch.float16),
+                                             (_lib.RF_ATTR_FLOAT32, np.uint32, torch.float32)):
+                dst = torch.full((count + 64,), -3.0, dtype=torch_t, device="cuda")
+                _lib.check(lib.rf_cast_accumulator(ptr(dsrc[start:]), count, attr_type, ptr(dst), stream))
+                torch.cuda.synchronize()
+                got = dst.cpu().numpy()
+                assert (got[count:] == -3.0).all(), (count, attr_type)       # nothing written past count
+                got = got[:count]
+                ref = want[start:start + count] if attr_type == _lib.RF_ATTR_FLOAT16 else src[start:start + count]
+                same = (got.view(np_t) == ref.view(np_t)) | (np.isnan(got) & np.isnan(ref))
+                assert same.all(), (count, start, attr_type, src[start:start + count][~same][:8], got[~same][:8])
+    dst = torch.full((8,), -3.0, dtype=torch.float16, device="cuda")
+    assert lib.rf_cast_accumulator(ptr(dsrc), 0, _lib.RF_ATTR_FLOAT16, ptr(dst), stream) == _lib.RF_OK
+    assert lib.rf_cast_accumulator(None, 0, _lib.RF_ATTR_FLOAT16, None, stream) == _lib.RF_OK
+    rc = lib.rf_cast_accumulator(ptr(dsrc), 8, 7, ptr(dst), stream)
+    assert rc != _lib.RF_OK and "Unsupported attribute type" in _lib.last_error()
+    with pytest.raises(RuntimeError, match="Unsupported attribute type"):
+        _lib.check(rc)
+    torch.cuda.synchronize()
+    assert (dst.cpu().numpy() == -3.0).all()
