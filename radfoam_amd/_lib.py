@@ -64,7 +64,7 @@ class LaunchOpts(C.Structure):
     ]
 
 
-# every symbol include/radfoam_hip.h declares: name -> (restype, argtypes)
+# every symbol include/radfoam_hip.h and include/radfoam_hip_geometry.h declare: name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
 _INT = C.c_int
@@ -114,6 +114,10 @@ SYMBOLS = {
     "rf_gate_tile_order": (_INT, [_P, C.POINTER(Camera), _P, _U32, _U32, C.c_float, _P, _P, _P, _P]),
     "rf_trace_benchmark": (_INT, [_INT, _INT, C.POINTER(TraceSettings), _U32, _P, _P, _U32, _P, _P, _P,
                                   C.POINTER(Camera), _P, _P, C.POINTER(LaunchOpts), _P]),
+    "rf_cell_geometry_workspace_bytes": (C.c_size_t, [_U32]),
+    "rf_cell_geometry": (_INT, [_P, _U32, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "rf_cell_surface_count": (_INT, [_U32, _P, _P, _U32, _P, _P, _P, _P]),
+    "rf_cell_surface_emit": (_INT, [_P, _U32, _P, _P, _U32, _P, _P, _P, _P, _U32, _P, _P, _P]),
 }
 
 _lib = None

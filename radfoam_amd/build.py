@@ -15,6 +15,12 @@ _CSRC = os.path.join(_HERE, "csrc")
 SOURCES = [os.path.join(_CSRC, n) for n in ("rf_kernels.hip", "rf_scene_ops.hip", "rf_adjacency.hip", "rf_grad_exchange.hip", "rf_delaunay.hip", "rf_tile_prior.hip")]
 HEADERS = [os.path.join(_CSRC, n) for n in ("rf_math.hpp", "rf_foam.hpp", "rf_wave.hpp", "rf_host.hpp", "rf_star.hpp", "rf_tiles.hpp")] + [
     os.path.join(os.path.dirname(_HERE), "include", "radfoam_hip.h")]
+# Built, linked and watched like SOURCES / HEADERS, but outside source_hash(): that hash names the tracer and triangulation
+# kernels the committed hardware counters and ISA constants (profiles/) were measured on.  What is listed here runs
+# beside them and changes none of their code, so adding or editing it must not turn that evidence stale.
+EXTRA_SOURCES = [os.path.join(_CSRC, n) for n in ("rf_cell_geometry.hip",)]
+EXTRA_HEADERS = [os.path.join(_CSRC, n) for n in ("rf_clip.hpp",)] + [
+    os.path.join(os.path.dirname(_HERE), "include", "radfoam_hip_geometry.h")]
 OBJ_DIR = os.path.join(_CSRC, "_obj")
 OUTPUT = os.path.join(_HERE, "libradfoam_hip.so")
 
@@ -41,7 +47,8 @@ def _stale(target: str, deps) -> bool:
 
 def source_hash() -> str:
     """sha256 over the kernel sources and headers, in a fixed order: what a set of hardware counters was measured on
-    (profiles/counters.json records it; bench.py refuses to quote counters of another build)."""
+    (profiles/counters.json records it; bench.py refuses to quote counters of another build).  EXTRA_SOURCES and
+    EXTRA_HEADERS are deliberately not part of it: see above."""
     import hashlib
 
     h = hashlib.sha256()
@@ -53,7 +60,7 @@ def source_hash() -> str:
 
 
 def needs_build() -> bool:
-    return _stale(OUTPUT, SOURCES + HEADERS)
+    return _stale(OUTPUT, SOURCES + HEADERS + EXTRA_SOURCES + EXTRA_HEADERS)
 
 
 def _run(cmd, verbose):
@@ -70,10 +77,11 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
     if not force and not needs_build():
         return OUTPUT
     os.makedirs(OBJ_DIR, exist_ok=True)
-    todo = [s for s in SOURCES if force or _stale(_object(s), [s] + HEADERS)]
+    sources, headers = SOURCES + EXTRA_SOURCES, HEADERS + EXTRA_HEADERS
+    todo = [s for s in sources if force or _stale(_object(s), [s] + headers)]
     with ThreadPoolExecutor(max_workers=max(1, len(todo))) as pool:
         list(pool.map(lambda s: _run([_hipcc()] + HIPCC_FLAGS + ["-c", s, "-o", _object(s)], verbose), todo))
-    _run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUTPUT] + [_object(s) for s in SOURCES],
+    _run([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUTPUT] + [_object(s) for s in sources],
          verbose)
     return OUTPUT
 

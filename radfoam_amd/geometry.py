@@ -1,0 +1,128 @@
+"""Voronoi cell geometry on the device: what a cell of the foam IS ("Cell geometry").
+
+  cell_geometry   volume, centroid, boundedness of every cell and the area of every face, in double
+  cell_surface    the faces between selected and unselected cells, as triangles: the foam's own watertight surface of
+                  e.g. ``density > tau``
+
+Cell ``a`` is the intersection of the half-spaces of its row of ``point_adjacency`` (taken as given); no tetrahedra are
+involved.  Both take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip behind the C-ABI of
+include/radfoam_hip_geometry.h; there is no CPU path.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import torch
+
+from . import _lib
+from .scene_ops import _check_f32_cuda, _ptr, _stream
+
+_STATUS_TEXT = {1: "a face outgrew 256 vertices while it was clipped",
+                2: "its adjacency row is malformed (offsets out of order, an index out of range, the site itself or "
+                   "a duplicate of it)"}
+
+
+class CellGeometry(NamedTuple):
+    volume: torch.Tensor      # f64[N]; +inf for an unbounded cell
+    centroid: torch.Tensor    # f64[N,3]; NaN for an unbounded cell
+    bounded: torch.Tensor     # bool[N]
+    face_area: torch.Tensor   # f64[E], aligned with point_adjacency; +inf for an unbounded face
+
+
+def _index_tensor(name, t, device):
+    """uint32 / int32 / int64 -> the uint32 words the kernels read (as a contiguous int32-typed tensor)."""
+    if not t.is_cuda or t.device != device:
+        raise RuntimeError(f"{name} must be a CUDA tensor on the device of points")
+    if t.dtype == torch.uint32:
+        return t.contiguous().view(torch.int32)
+    if t.dtype == torch.int32:
+        return t.contiguous()
+    if t.dtype == torch.int64:
+        return t.to(torch.int32).contiguous()     # values below 2^32 keep their low word
+    raise RuntimeError("point_adjacency and point_adjacency_offsets must have uint32, int32 or int64 dtype")
+
+
+def _prepare(points, point_adjacency, point_adjacency_offsets):
+    _check_f32_cuda("points", points)
+    if points.dim() != 2 or points.size(-1) != 3:
+        raise RuntimeError("points must be [N,3]")
+    p = points.detach().contiguous()
+    adj = _index_tensor("point_adjacency", point_adjacency, p.device)
+    off = _index_tensor("point_adjacency_offsets", point_adjacency_offsets, p.device)
+    if adj.dim() != 1 or off.dim() != 1 or off.numel() != p.size(0) + 1:
+        raise RuntimeError("expected point_adjacency [E] and point_adjacency_offsets [N+1]")
+    if p.size(0) >= 2 ** 32 - 1 or adj.numel() >= 2 ** 32:
+        raise RuntimeError("more than 2^32 points or adjacency entries")
+    bbox = (torch.cat([p.min(0).values, p.max(0).values]) if p.size(0)
+            else torch.zeros(6, dtype=torch.float32, device=p.device))
+    return p, adj, off, bbox
+
+
+def _run_geometry(p, adj, off, bbox):
+    """(CellGeometry, face_vertices int32[E]); one synchronisation, to read whether a cell was refused."""
+    n, e, dev = p.size(0), adj.numel(), p.device
+    lib = _lib.load()
+    volume = torch.empty(n, dtype=torch.float64, device=dev)
+    centroid = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    bounded = torch.empty(n, dtype=torch.uint8, device=dev)
+    face_area = torch.empty(e, dtype=torch.float64, device=dev)
+    face_vertices = torch.empty(e, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rf_cell_geometry_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.rf_cell_geometry(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(volume), _ptr(centroid),
+                                  _ptr(bounded), _ptr(face_area), _ptr(face_vertices), _ptr(status), _ptr(ws),
+                                  ws.numel(), _stream(dev))
+    _lib.check(rc)
+    if n:
+        worst, cell = status.max(0)
+        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
+        if worst:
+            raise RuntimeError(f"cell_geometry: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    return CellGeometry(volume, centroid, bounded.bool(), face_area), face_vertices
+
+
+def cell_geometry(points: torch.Tensor, point_adjacency: torch.Tensor,
+                  point_adjacency_offsets: torch.Tensor) -> CellGeometry:
+    """Volume f64[N], centroid f64[N,3], bounded bool[N] of every Voronoi cell and face_area f64[E] of every face
+    (aligned with ``point_adjacency``), computed in double from the fp32 points.
+
+    A face is the bisector plane of (a,b) clipped by the other half-spaces of a's row, starting from a square of
+    half-side 4 * |bbox diagonal|; it is unbounded (area +inf) when a piece of that square survives.  A cell with an
+    unbounded face, or with no neighbours, is unbounded: volume +inf, centroid NaN, bounded False; its bounded faces
+    keep their finite areas.  Index tensors may be uint32, int32 or int64.  Raises RuntimeError naming the cell if a
+    face needs more than 256 vertices or a row is malformed."""
+    return _run_geometry(*_prepare(points, point_adjacency, point_adjacency_offsets))[0]
+
+
+def cell_surface(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
+                 inside: torch.Tensor):
+    """(triangles f64[T,3,3], edge int64[T]): every face between a cell with ``inside`` set and a neighbour without, as
+    a triangle fan wound so that its normal points out of the inside cell; ``edge`` is the adjacency slot each triangle
+    came from.  The order is that of the adjacency slots: deterministic.  Vertices are not welded.
+
+    Raises ValueError if ``inside`` selects an unbounded cell (its surface would not close)."""
+    p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+    n, e, dev = p.size(0), adj.numel(), p.device
+    if not inside.is_cuda or inside.device != dev or inside.dtype != torch.bool or inside.shape != (n,):
+        raise RuntimeError("inside must be a bool[N] CUDA tensor on the device of points")
+    geo, face_vertices = _run_geometry(p, adj, off, bbox)
+    if bool((inside & ~geo.bounded).any()):
+        raise ValueError("cell_surface: inside selects an unbounded cell")
+    lib = _lib.load()
+    mask = inside.contiguous().view(torch.uint8)
+    counts = torch.zeros(e, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.rf_cell_surface_count(n, _ptr(adj), _ptr(off), e, _ptr(mask), _ptr(face_vertices), _ptr(counts),
+                                             _stream(dev)))
+    slots = torch.nonzero(counts).reshape(-1)                      # ascending adjacency slots
+    ends = torch.cumsum(counts[slots], 0, dtype=torch.int64)
+    total = int(ends[-1]) if slots.numel() else 0
+    begins = (ends - counts[slots]).contiguous()
+    triangles = torch.empty((total, 3, 3), dtype=torch.float64, device=dev)
+    edge = torch.empty(total, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.rf_cell_surface_emit(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(face_vertices),
+                                            _ptr(slots), _ptr(begins), slots.numel(), _ptr(triangles), _ptr(edge),
+                                            _stream(dev)))
+    return triangles, edge
