@@ -64,7 +64,7 @@ class LaunchOpts(C.Structure):
     ]
 
 
-# every symbol include/radfoam_hip.h and include/radfoam_hip_geometry.h declare: name -> (restype, argtypes)
+# every symbol include/radfoam_hip.h, radfoam_hip_geometry.h and radfoam_hip_segments.h declare: name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
 _INT = C.c_int
@@ -118,6 +118,8 @@ SYMBOLS = {
     "rf_cell_geometry": (_INT, [_P, _U32, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "rf_cell_surface_count": (_INT, [_U32, _P, _P, _U32, _P, _P, _P, _P]),
     "rf_cell_surface_emit": (_INT, [_P, _U32, _P, _P, _U32, _P, _P, _P, _P, _U32, _P, _P, _P]),
+    "rf_trace_segments_count": (_INT, [C.POINTER(TraceSettings), _U32, _U32, _P, _U32, _P, _P, _P, _P, _P]),
+    "rf_trace_segments_fill": (_INT, [C.POINTER(TraceSettings), _U32, _U32, _P, _U32, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1183,6 +1183,68 @@ class Pipeline:
             out["visited"] = marks.bool()
         return out
 
+    def trace_segments(self, points, attributes, point_adjacency, point_adjacency_offsets, rays, start_point,
+                       weight_threshold=None, max_intersections=None):
+        """The walk of every ray as data: the cells it scans, in order, with the ray parameters at which it enters and
+        leaves each -- what ``trace_forward`` composites over, for callers that shade differently (an MLP colour, extra
+        per-cell features, a loss over the intervals, an occlusion query).  ``radfoam.composite_segments`` composites
+        such a list in torch, differentiably.  Arguments and their validation are ``trace_forward``'s.
+
+        Rays of any leading shape are flattened in row-major order (R rays).  Returns a ragged list in CSR form:
+
+          offsets            int64 [R+1]    entries of ray r are offsets[r]:offsets[r+1]; offsets[0] = 0
+          cells              uint32 [S]     the cell scanned at each step; a ray's first entry is its start_point
+          t_exit             float32 [S]    where the walk leaves that cell; +inf when it has no exit (the walk ends there)
+          t_enter            float32 [S]    the t0 the compositing used: 0 first, then the running maximum of the earlier t_exit
+          num_intersections  uint32, batch shape + (1,): trace_forward's output for the same call
+
+        Ray r has min(num_intersections[r], max_intersections) entries (the step that overruns max_intersections is
+        counted, not scanned); entries with t_exit <= t_enter stay in the list (the compositing gives them weight 0).
+        The walk ends where trace_forward's ends and never reads a colour row; an fp16 pipeline walks as an fp32 one
+        given the widened attributes.  A start_point that is not a cell gives a ray without entries.
+
+        Two launches (rf_trace_segments_count, rf_trace_segments_fill) around a prefix sum on the device.  Allocating
+        the [S] outputs needs S on the host: the call synchronises with the device ONCE, between the two launches.
+        Uses the pipeline's packed-foam cache; the hop trail and the tile orders of trace_forward / trace_backward are
+        left alone."""
+        points_c = points.contiguous()
+        attributes_c = attributes.contiguous()
+        adjacency_c = point_adjacency.contiguous()
+        offsets_c = point_adjacency_offsets.contiguous()
+        rays_c = rays.contiguous()
+        start_c = start_point.contiguous()
+        self._validate_scene_data(points, attributes, point_adjacency, point_adjacency_offsets)
+        num_points = points_c.size(0)
+        num_rays = self._validate_rays(rays_c, start_c)
+        dev = rays_c.device
+        settings = self._settings(weight_threshold, max_intersections)
+
+        batch = tuple(rays_c.shape[:-1])
+        num_intersections = torch.empty(batch + (1,), dtype=torch.uint32, device=dev)
+        offsets = torch.zeros(num_rays + 1, dtype=torch.int64, device=dev)
+        total = 0
+        if num_rays:
+            # packs the workspace unless it is cached for these tensors (no ray shape: no tile-order state is looked up)
+            self.prepare_foam(points, attributes, point_adjacency, point_adjacency_offsets)
+            ws = self._cache.workspace
+            walk = (C.byref(settings), num_points, adjacency_c.numel(), _ptr(ws), num_rays, _ptr(rays_c), _ptr(start_c))
+            counts = torch.empty(num_rays, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                rc = self._lib.rf_trace_segments_count(*walk, _ptr(counts), _ptr(num_intersections), _stream_ptr(dev))
+            _lib.check(rc)
+            torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+            total = int(offsets[-1])                  # the one synchronisation
+        cells = torch.empty(total, dtype=torch.uint32, device=dev)
+        t_enter = torch.empty(total, dtype=torch.float32, device=dev)
+        t_exit = torch.empty(total, dtype=torch.float32, device=dev)
+        if total:
+            with torch.cuda.device(dev):
+                rc = self._lib.rf_trace_segments_fill(*walk, _ptr(offsets), _ptr(cells), _ptr(t_enter), _ptr(t_exit),
+                                                      _stream_ptr(dev))
+            _lib.check(rc)
+        return {"offsets": offsets, "cells": cells, "t_exit": t_exit, "t_enter": t_enter,
+                "num_intersections": num_intersections}
+
     def build_adjacent_diff(self, points, point_adjacency, point_adjacency_offsets):
         """half4 neighbour-offset table [E,4] (prefetch_adjacent_diff, pipeline.cu:546-586; the
         table benchmark.py:44-54 builds in torch)."""
