@@ -1,11 +1,12 @@
 /*
  * radfoam_hip_segments.h -- C-ABI of the walk export (libradfoam_hip.so, rf_segments.hip): the cells every ray
- * scans, in order, with the ray parameters at which it enters and leaves each.
+ * scans, in order, with the ray parameters at which it enters and leaves each, and of its
+ * gradient with respect to the points (rf_segments_grad.hip, section 4.9).
  *
  * Conventions of radfoam_hip.h: every pointer is a DEVICE pointer, `stream` is a hipStream_t passed as void*, every
  * function returns RF_OK or a negative rf_status and leaves a message for rf_last_error.  Nothing synchronises.
  *
- * Both functions read the PREPARED workspace of rf_prepare_foam (any sh_degree / attr_type: the part of the layout
+ * The walk functions read the PREPARED workspace of rf_prepare_foam (any sh_degree / attr_type: the part of the layout
  * they read -- cell records, fp16 face blocks, links, padded offsets -- depends on num_points and
  * point_adjacency_size alone) and walk exactly as rf_trace_forward does with the same settings: the reference's scan
  * (every face divided, smallest rounded quotient, lowest index among equals), the same transmittance test, the same
@@ -41,6 +42,30 @@ int rf_trace_segments_fill(const rf_trace_settings *settings, uint32_t num_point
                            const void *workspace, uint32_t num_rays, const float *rays,
                            const uint32_t *start_point_index, const int64_t *offsets, uint32_t *cells, float *t_enter,
                            float *t_exit, void *stream);
+
+/* The cell behind every ray's last face: exit_cells[num_rays] (uint32).  One lane per ray scans
+ * the cell of the ray's last entry again over the same prepared workspace, exactly as the walk did, and follows the
+ * winner's link.  0xFFFFFFFF where the ray has no entries or the t_exit of its last entry is +inf.  offsets / cells /
+ * t_exit are what rf_trace_segments_fill wrote for the same rays and workspace. */
+int rf_trace_segments_exit_cells(uint32_t num_points, uint32_t point_adjacency_size, const void *workspace,
+                                 uint32_t num_rays, const float *rays, const int64_t *offsets, const uint32_t *cells,
+                                 const float *t_exit, uint32_t *exit_cells, void *stream);
+
+/* Gradient of a loss with respect to the points through the stored t_enter / t_exit (rf_segments_grad.hip; DESIGN.md
+ * section 4.9).  Face j lies between a = cells[j] and b = the next cell of the walk (cells[j + 1] inside the ray's
+ * range, exit_cells[r] behind the ray's last entry, none where t_exit[j] is +inf or exit_cells[r] is 0xFFFFFFFF);
+ * entry j HOLDS the running maximum iff t_exit[j] > t_enter[j];
+ *     G_j = grad_t_exit[j] + [j holds] * (sum of grad_t_enter[m] over the ray's entries after j, up to and including
+ *           the next holder)
+ *     points_grad[a] += G_j dt/dp_a,  points_grad[b] += G_j dt/dp_b     (nothing where G_j == 0 exactly)
+ * with the derivatives of the exact fp32 bisector of (p_a, p_b), as rf_trace_backward forms them.  One lane per entry:
+ * entry_ray[num_entries] (int32) names the ray of every entry; num_entries = offsets[num_rays].  points_grad
+ * [num_points][3] (fp32) is ACCUMULATED into with atomics: the caller zeroes it.  Rays get no gradient. */
+int rf_segments_points_grad(uint32_t num_points, const float *points, uint32_t num_rays, const float *rays,
+                            const int64_t *offsets, int64_t num_entries, const int32_t *entry_ray,
+                            const uint32_t *cells, const float *t_enter, const float *t_exit,
+                            const uint32_t *exit_cells, const float *grad_t_enter, const float *grad_t_exit,
+                            float *points_grad, void *stream);
 
 #ifdef __cplusplus
 }

@@ -214,6 +214,48 @@ static int launch_segments(bool fill, const char *what, const rf_trace_settings 
     return check_launch(what);
 }
 
+// The cell behind every ray's last face.  A ray that ends on the threshold or the step limit
+// leaves its last entry with a finite t_exit, and the cell on the far side of that face is not in the list.  One lane
+// per ray scans the last entry's cell again -- seg_scan over the same workspace, hence the winner the walk found -- and
+// follows its link.  kNone where the ray has no entries or its last exit is infinite.
+struct SegExitParams {
+    const float4 *cells;
+    const uint32_t *geo;
+    const Link *link;
+    const uint32_t *poff;
+    uint32_t num_points, num_rays;
+    const float *rays;
+    const int64_t *offsets;
+    const uint32_t *seg_cells;
+    const float *t_exit;
+    uint32_t *exit_cells;
+};
+
+__global__ __launch_bounds__(kSegBlock) void segments_exit_cells_kernel(SegExitParams p) {
+    const uint32_t ray = blockIdx.x * (uint32_t)kSegBlock + threadIdx.x;
+    if (ray >= p.num_rays) return;
+    uint32_t out = kNone;
+    const int64_t lo = p.offsets[ray], hi = p.offsets[ray + 1];
+    if (hi > lo) {
+        const uint32_t cur = p.seg_cells[hi - 1];
+        if (p.t_exit[hi - 1] != __builtin_inff() && cur < p.num_points) {
+            const float *rp = p.rays + (size_t)ray * 6;
+            const float Ox = rp[0], Oy = rp[1], Oz = rp[2];
+            float dx = rp[3], dy = rp[4], dz = rp[5];
+            const float nrm = sqrtf(dot3(dx, dy, dz, dx, dy, dz));
+            dx = dx / nrm;
+            dy = dy / nrm;
+            dz = dz / nrm;
+            const uint32_t nb = p.poff[cur];
+            const uint32_t cnt = p.poff[cur + 1] - nb;
+            const float4 head = p.cells[cur];
+            const SegExit sr = seg_scan(p.geo + (size_t)(nb >> 2) * 6u, cnt, head.x, head.y, head.z, Ox, Oy, Oz, dx, dy, dz);
+            if (sr.k != kNone) out = p.link[nb + sr.k].nbr;
+        }
+    }
+    p.exit_cells[ray] = out;
+}
+
 }  // namespace rf
 
 using namespace rf;
@@ -245,6 +287,34 @@ int rf_trace_segments_fill(const rf_trace_settings *settings, uint32_t num_point
     p.t_exit = t_exit;
     return launch_segments(true, "rf_trace_segments_fill", settings, num_points, point_adjacency_size, workspace,
                            num_rays, rays, start_point_index, p, stream);
+}
+
+int rf_trace_segments_exit_cells(uint32_t num_points, uint32_t point_adjacency_size, const void *workspace,
+                                 uint32_t num_rays, const float *rays, const int64_t *offsets, const uint32_t *cells,
+                                 const float *t_exit, uint32_t *exit_cells, void *stream) {
+    const char *what = "rf_trace_segments_exit_cells";
+    g_err[0] = 0;
+    if (num_rays == 0) return RF_OK;
+    // (cells / t_exit may be null when the offsets say that no ray has an entry: nothing of them is read then)
+    if (!rays || !offsets || !exit_cells || (num_points && !workspace))
+        return fail(RF_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+    const FoamLayout L = foam_layout(num_points, point_adjacency_size, 0, 0);
+    const char *ws = static_cast<const char *>(workspace);
+    SegExitParams p{};
+    p.cells = reinterpret_cast<const float4 *>(ws + L.cells_off);
+    p.geo = reinterpret_cast<const uint32_t *>(ws + L.geo_off);
+    p.link = reinterpret_cast<const Link *>(ws + L.link_off);
+    p.poff = reinterpret_cast<const uint32_t *>(ws + L.poff_off);
+    p.num_points = num_points;
+    p.num_rays = num_rays;
+    p.rays = rays;
+    p.offsets = offsets;
+    p.seg_cells = cells;
+    p.t_exit = t_exit;
+    p.exit_cells = exit_cells;
+    const dim3 grid((num_rays + (uint32_t)kSegBlock - 1u) / (uint32_t)kSegBlock), block(kSegBlock);
+    hipLaunchKernelGGL(segments_exit_cells_kernel, grid, block, 0, static_cast<hipStream_t>(stream), p);
+    return check_launch(what);
 }
 
 }  // extern "C"

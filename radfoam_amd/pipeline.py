@@ -1245,6 +1245,42 @@ class Pipeline:
         return {"offsets": offsets, "cells": cells, "t_exit": t_exit, "t_enter": t_enter,
                 "num_intersections": num_intersections}
 
+    def trace_differentiable_segments(self, points, attributes, point_adjacency, point_adjacency_offsets, rays,
+                                      start_point, weight_threshold=None, max_intersections=None):
+        """``trace_segments`` whose ``t_enter`` / ``t_exit`` are differentiable in ``points``, so that
+        ``radfoam.composite_segments`` and any other torch function of the intervals moves the sites.  Arguments,
+        validation and the returned dict are ``trace_segments``'; one more entry:
+
+          exit_cells         uint32 [R]     the cell behind the face of every ray's last entry (a walk that ends on the
+                                            threshold or the step limit stops in front of it); 0xFFFFFFFF where the ray
+                                            has no entries or its last t_exit is +inf
+
+        The values of ``t_enter`` / ``t_exit`` are the stored ones, bit for bit.  With ``points.requires_grad`` they come
+        out of a ``torch.autograd.Function`` whose backward is ``radfoam.segment_points_grad`` (the exact fp32 bisector's
+        derivative, as ``trace_backward`` uses; the cell sequence is held fixed; rays and attributes get no gradient);
+        otherwise they are plain tensors.  One launch more than ``trace_segments`` (rf_trace_segments_exit_cells, on
+        the same cached workspace); the hop trail and the tile orders are left alone."""
+        seg = self.trace_segments(points, attributes, point_adjacency, point_adjacency_offsets, rays, start_point,
+                                  weight_threshold, max_intersections)
+        rays_c = rays.contiguous()
+        dev = rays_c.device
+        num_rays = seg["offsets"].numel() - 1
+        exit_cells = torch.full((num_rays,), -1, dtype=torch.int32, device=dev).view(torch.uint32)
+        if seg["cells"].numel():
+            with torch.cuda.device(dev):
+                rc = self._lib.rf_trace_segments_exit_cells(
+                    points.size(0), point_adjacency.numel(), _ptr(self._cache.workspace), num_rays, _ptr(rays_c),
+                    _ptr(seg["offsets"]), _ptr(seg["cells"]), _ptr(seg["t_exit"]), _ptr(exit_cells), _stream_ptr(dev))
+            _lib.check(rc)
+        seg["exit_cells"] = exit_cells
+        if points.requires_grad and torch.is_grad_enabled():
+            from .segments import _SegmentTimes
+
+            seg["t_enter"], seg["t_exit"] = _SegmentTimes.apply(
+                points, rays_c.detach().reshape(-1, 6), seg["offsets"], seg["cells"], exit_cells, seg["t_enter"],
+                seg["t_exit"])
+        return seg
+
     def build_adjacent_diff(self, points, point_adjacency, point_adjacency_offsets):
         """half4 neighbour-offset table [E,4] (prefetch_adjacent_diff, pipeline.cu:546-586; the
         table benchmark.py:44-54 builds in torch)."""

@@ -1,7 +1,11 @@
 """Compositing over an exported walk (``Pipeline.trace_segments``) in plain torch, so that a caller's own shading model --
 any per-cell density and colour it can compute with autograd -- is rendered along the very intervals the tracer uses.
 
-No kernel of its own: a handful of elementwise operations, one cumulative sum and two scatter-adds over the [S] entries.
+``composite_segments`` has no kernel of its own: a handful of elementwise operations, one cumulative sum and two
+scatter-adds over the [S] entries.  It reads ``t_enter`` / ``t_exit`` with ordinary torch operations, so when those two
+carry a ``grad_fn`` with respect to the points (``Pipeline.trace_differentiable_segments``) everything composited from
+them is differentiable in the geometry.  The backward operator behind that is ``segment_points_grad``: a HIP kernel
+(rf_segments_grad.hip) on the device, a vectorised torch restatement of the same definition elsewhere.
 """
 from __future__ import annotations
 
@@ -56,3 +60,153 @@ def composite_segments(seg, density: torch.Tensor, rgb: torch.Tensor) -> torch.T
     colour = out[:, :3].index_add(0, ray, weight.unsqueeze(-1) * rgb[cells].to(torch.float64))
     alpha = -torch.expm1(run0[offsets[1:]] - before)
     return torch.cat([colour, alpha.unsqueeze(-1)], dim=-1).to(dtype)
+
+
+_NONE = 0xFFFFFFFF
+
+
+def _check_segment_grad_inputs(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit):
+    if points.dim() != 2 or points.size(-1) != 3:
+        raise RuntimeError("expected points [N, 3]")
+    if points.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("points must have float32 or float64 dtype")
+    offsets = seg["offsets"]
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise RuntimeError("seg['offsets'] must be int64 [R+1]")
+    num_rays, total = offsets.numel() - 1, seg["cells"].numel()
+    if seg["t_enter"].numel() != total or seg["t_exit"].numel() != total:
+        raise RuntimeError("seg['cells'], seg['t_enter'] and seg['t_exit'] must have one element per entry")
+    if grad_t_enter.numel() != total or grad_t_exit.numel() != total:
+        raise RuntimeError("grad_t_enter and grad_t_exit must have one element per entry")
+    if exit_cells.numel() != num_rays:
+        raise RuntimeError("exit_cells must have one element per ray")
+    if rays.size(-1) != 6 or rays.numel() != 6 * num_rays:
+        raise RuntimeError("rays must have one row of 6 per ray")
+    return num_rays, total
+
+
+def _segment_points_grad_torch(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, num_rays, total):
+    """DESIGN 4.9, restated with torch operations over all S entries at once, in the dtype of ``points``."""
+    dev, dtype = points.device, points.dtype
+    out = torch.zeros_like(points)
+    if total == 0:
+        return out
+    offsets = seg["offsets"].to(dev)
+    cells = seg["cells"].to(dev).to(torch.int64)
+    t_enter, t_exit = seg["t_enter"].to(dev), seg["t_exit"].to(dev)      # holders: from the stored floats
+    g_enter, g_exit = grad_t_enter.to(dev).to(dtype).reshape(-1), grad_t_exit.to(dev).to(dtype).reshape(-1)
+    exits = exit_cells.to(dev).to(torch.int64) & _NONE
+    counts = offsets[1:] - offsets[:-1]
+    ray = torch.repeat_interleave(torch.arange(num_rays, device=dev), counts, output_size=total)
+    index = torch.arange(total, device=dev)
+
+    # the cell behind face j: the next entry, or exit_cells behind a ray's last entry; none behind an infinite exit
+    last = index == offsets[1:][ray] - 1
+    after = torch.where(last, exits[ray], torch.cat([cells[1:], cells.new_zeros(1)]))
+    has_next = torch.isfinite(t_exit) & (after != _NONE)
+
+    # t_enter[m] is the t_exit of the last holder in front of m within the ray (0, a constant, when there is none)
+    holder = t_exit > t_enter
+    latest = torch.cummax(torch.where(holder, index, index.new_full((), -1)), 0).values
+    held_by = torch.cat([latest.new_full((1,), -1), latest[:-1]])
+    owned = held_by >= offsets[:-1][ray]
+    total_grad = g_exit.index_add(0, held_by.clamp_min(0), torch.where(owned, g_enter, torch.zeros_like(g_enter)))
+
+    live = has_next & (total_grad != 0)                                   # G == 0 exactly adds nothing: no 0 * inf
+    r = rays.to(dev).reshape(-1, 6).to(dtype)
+    origin = r[:, :3][ray]
+    direction = (r[:, 3:] / (r[:, 3:] * r[:, 3:]).sum(-1, keepdim=True).sqrt())[ray]
+    pa = points.detach()[cells]
+    pb = points.detach()[torch.where(has_next, after, torch.zeros_like(after))]
+    normal = pb - pa
+    num = (((pa + pb) / 2 - origin) * normal).sum(-1, keepdim=True)
+    dp = (normal * direction).sum(-1, keepdim=True)
+    den = dp * dp
+    weight = total_grad.unsqueeze(-1)
+    zero = torch.zeros_like(pa)
+    live = live.unsqueeze(-1)
+    grad_a = torch.where(live, weight * ((num * direction + dp * (origin - pa)) / den), zero)
+    grad_b = torch.where(live, weight * (-(num * direction + dp * (origin - pb)) / den), zero)
+    out.index_add_(0, cells, grad_a)
+    out.index_add_(0, torch.where(has_next, after, torch.zeros_like(after)), grad_b)
+    return out
+
+
+def segment_points_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, backend=None) -> torch.Tensor:
+    """dL/dpoints [N, 3] from dL/dt_enter [S] and dL/dt_exit [S] of the walk ``seg`` (the dict
+    ``Pipeline.trace_differentiable_segments`` returns; ``exit_cells`` uint32 [R] is its entry of that name: the cell
+    behind every ray's last face, 0xFFFFFFFF for none).  DESIGN 4.9:
+
+        face j lies between a = cells[j] and b = the next cell of the walk; none where t_exit[j] is infinite
+        j holds the running maximum iff t_exit[j] > t_enter[j] (the stored floats decide)
+        G_j = grad_t_exit[j] + [j holds] * sum of grad_t_enter over the ray's later entries up to the next holder, included
+        points_grad[a] += G_j dt/dp_a,  points_grad[b] += G_j dt/dp_b         (nothing where G_j == 0 exactly)
+
+    with t the crossing of the ray (origin, normalised direction) and the exact bisector of (p_a, p_b) -- the
+    derivative ``trace_backward`` uses, not that of the fp16 face table the walk ran on.  The gradient of t_enter in
+    front of a ray's first holder is dropped (t_enter is the constant 0 there).  Rays get no gradient; a grazing face
+    may give non-finite values, as in ``trace_backward``.
+
+    CUDA tensors go through the HIP kernel (float32 points; one lane per entry, atomics into a zeroed [N, 3]).  CPU
+    tensors, and CUDA tensors with ``backend="torch"``, go through a vectorised torch restatement in the dtype of
+    ``points`` (float32 or float64): no Python loop over rays."""
+    if backend not in (None, "hip", "torch"):
+        raise ValueError("backend must be None, 'hip' or 'torch'")
+    num_rays, total = _check_segment_grad_inputs(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit)
+    if backend is None:
+        backend = "hip" if points.is_cuda else "torch"
+    if backend == "torch":
+        return _segment_points_grad_torch(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, num_rays, total)
+
+    from . import _lib
+    from .pipeline import _ptr, _stream_ptr
+
+    if not points.is_cuda or points.dtype != torch.float32:
+        raise RuntimeError("the kernel takes float32 CUDA points (backend='torch' restates it for anything else)")
+    dev = points.device
+    out = torch.zeros((points.size(0), 3), dtype=torch.float32, device=dev)
+    if total == 0 or points.size(0) == 0:
+        return out
+    if num_rays >= 2 ** 31:
+        raise RuntimeError("too many rays for an int32 ray index")
+
+    def f32(t):
+        return t.detach().to(dev).to(torch.float32).reshape(-1).contiguous()
+
+    points_c = points.detach().contiguous()
+    rays_c = rays.detach().to(dev).to(torch.float32).reshape(-1, 6).contiguous()
+    offsets = seg["offsets"].to(dev).contiguous()
+    cells = seg["cells"].to(dev).contiguous()
+    exits = exit_cells.to(dev).contiguous()
+    if cells.dtype != torch.uint32 or exits.dtype != torch.uint32:
+        raise RuntimeError("seg['cells'] and exit_cells must have uint32 dtype")
+    t_enter, t_exit = f32(seg["t_enter"]), f32(seg["t_exit"])
+    g_enter, g_exit = f32(grad_t_enter), f32(grad_t_exit)
+    counts = offsets[1:] - offsets[:-1]
+    entry_ray = torch.repeat_interleave(torch.arange(num_rays, dtype=torch.int32, device=dev), counts, output_size=total)
+    with torch.cuda.device(dev):
+        rc = _lib.load().rf_segments_points_grad(
+            points_c.size(0), _ptr(points_c), num_rays, _ptr(rays_c), _ptr(offsets), total, _ptr(entry_ray),
+            _ptr(cells), _ptr(t_enter), _ptr(t_exit), _ptr(exits), _ptr(g_enter), _ptr(g_exit), _ptr(out),
+            _stream_ptr(dev))
+    _lib.check(rc)
+    return out
+
+
+class _SegmentTimes(torch.autograd.Function):
+    """t_enter / t_exit of a walk as functions of the points: the forward hands back the stored tensors, the backward
+    is ``segment_points_grad``."""
+
+    @staticmethod
+    def forward(ctx, points, rays, offsets, cells, exit_cells, t_enter, t_exit):
+        ctx.save_for_backward(points, rays, offsets, cells, exit_cells, t_enter, t_exit)
+        return t_enter, t_exit
+
+    @staticmethod
+    def backward(ctx, grad_t_enter, grad_t_exit):
+        points, rays, offsets, cells, exit_cells, t_enter, t_exit = ctx.saved_tensors
+        seg = {"offsets": offsets, "cells": cells, "t_enter": t_enter, "t_exit": t_exit}
+        grad_t_enter = torch.zeros_like(t_enter) if grad_t_enter is None else grad_t_enter
+        grad_t_exit = torch.zeros_like(t_exit) if grad_t_exit is None else grad_t_exit
+        grad = segment_points_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit)
+        return grad.to(points.dtype), None, None, None, None, None, None
