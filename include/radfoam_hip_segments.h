@@ -1,7 +1,8 @@
 /*
  * radfoam_hip_segments.h -- C-ABI of the walk export (libradfoam_hip.so, rf_segments.hip): the cells every ray
  * scans, in order, with the ray parameters at which it enters and leaves each, and of its
- * gradient with respect to the points (rf_segments_grad.hip, section 4.9).
+ * gradient with respect to the points (rf_segments_grad.hip, section 4.9) and to the rays (rf_segments_rays_grad.hip,
+ * section 4.10).
  *
  * Conventions of radfoam_hip.h: every pointer is a DEVICE pointer, `stream` is a hipStream_t passed as void*, every
  * function returns RF_OK or a negative rf_status and leaves a message for rf_last_error.  Nothing synchronises.
@@ -60,12 +61,27 @@ int rf_trace_segments_exit_cells(uint32_t num_points, uint32_t point_adjacency_s
  *     points_grad[a] += G_j dt/dp_a,  points_grad[b] += G_j dt/dp_b     (nothing where G_j == 0 exactly)
  * with the derivatives of the exact fp32 bisector of (p_a, p_b), as rf_trace_backward forms them.  One lane per entry:
  * entry_ray[num_entries] (int32) names the ray of every entry; num_entries = offsets[num_rays].  points_grad
- * [num_points][3] (fp32) is ACCUMULATED into with atomics: the caller zeroes it.  Rays get no gradient. */
+ * [num_points][3] (fp32) is ACCUMULATED into with atomics: the caller zeroes it.  The rays' gradient is
+ * rf_segments_rays_grad's. */
 int rf_segments_points_grad(uint32_t num_points, const float *points, uint32_t num_rays, const float *rays,
                             const int64_t *offsets, int64_t num_entries, const int32_t *entry_ray,
                             const uint32_t *cells, const float *t_enter, const float *t_exit,
                             const uint32_t *exit_cells, const float *grad_t_enter, const float *grad_t_exit,
                             float *points_grad, void *stream);
+
+/* Gradient of the same loss with respect to the RAYS (rf_segments_rays_grad.hip).  Arguments,
+ * faces, holders and G_j as above; with n = p_b - p_a, m = (p_a + p_b) / 2, O / D the ray's origin / stored direction,
+ * d = D / |D|, num = (m - O) . n and dp = n . d (the crossing is t = num / dp; the cell sequence is held fixed):
+ *     ray_grad[r][0:3] += sum over the ray's entries of G_j * (-n / dp)
+ *     ray_grad[r][3:6] += sum over the ray's entries of G_j * (-num / (dp^2 |D|)) * (n - dp d)
+ * Nothing where G_j == 0 exactly or the face has no next cell; dp = 0 gives non-finite values in that ray's row only.
+ * One lane per entry; a ray's contributions are summed in double within the wave and its row gets at most one atomic
+ * update per wave the ray reaches into.  Entries whose entry_ray is out of range or does not match the offsets add
+ * nothing.  ray_grad [num_rays][6] (fp32) is ACCUMULATED into: the caller zeroes it. */
+int rf_segments_rays_grad(uint32_t num_points, const float *points, uint32_t num_rays, const float *rays,
+                          const int64_t *offsets, int64_t num_entries, const int32_t *entry_ray, const uint32_t *cells,
+                          const float *t_enter, const float *t_exit, const uint32_t *exit_cells,
+                          const float *grad_t_enter, const float *grad_t_exit, float *ray_grad, void *stream);
 
 #ifdef __cplusplus
 }

@@ -122,6 +122,7 @@ SYMBOLS = {
     "rf_trace_segments_fill": (_INT, [C.POINTER(TraceSettings), _U32, _U32, _P, _U32, _P, _P, _P, _P, _P, _P, _P]),
     "rf_trace_segments_exit_cells": (_INT, [_U32, _U32, _P, _U32, _P, _P, _P, _P, _P, _P]),
     "rf_segments_points_grad": (_INT, [_U32, _P, _U32, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rf_segments_rays_grad": (_INT, [_U32, _P, _U32, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1255,11 +1255,14 @@ class Pipeline:
                                             threshold or the step limit stops in front of it); 0xFFFFFFFF where the ray
                                             has no entries or its last t_exit is +inf
 
-        The values of ``t_enter`` / ``t_exit`` are the stored ones, bit for bit.  With ``points.requires_grad`` they come
-        out of a ``torch.autograd.Function`` whose backward is ``radfoam.segment_points_grad`` (the exact fp32 bisector's
-        derivative, as ``trace_backward`` uses; the cell sequence is held fixed; rays and attributes get no gradient);
-        otherwise they are plain tensors.  One launch more than ``trace_segments`` (rf_trace_segments_exit_cells, on
-        the same cached workspace); the hop trail and the tile orders are left alone."""
+        The values of ``t_enter`` / ``t_exit`` are the stored ones, bit for bit.  With ``points.requires_grad`` or
+        ``rays.requires_grad`` they come out of a ``torch.autograd.Function`` whose backward is
+        ``radfoam.segment_points_grad`` for the points and ``radfoam.segment_rays_grad`` for the rays (DESIGN 4.10;
+        float32, in the shape of ``rays``), each run only where its input requires a gradient (the exact fp32
+        bisector's derivative, as ``trace_backward`` uses; the cell sequence and the start cells are held fixed;
+        attributes get no gradient); otherwise they are plain tensors.  One launch more than ``trace_segments``
+        (rf_trace_segments_exit_cells, on the same cached workspace); the hop trail and the tile orders are left
+        alone."""
         seg = self.trace_segments(points, attributes, point_adjacency, point_adjacency_offsets, rays, start_point,
                                   weight_threshold, max_intersections)
         rays_c = rays.contiguous()
@@ -1273,12 +1276,12 @@ class Pipeline:
                     _ptr(seg["offsets"]), _ptr(seg["cells"]), _ptr(seg["t_exit"]), _ptr(exit_cells), _stream_ptr(dev))
             _lib.check(rc)
         seg["exit_cells"] = exit_cells
-        if points.requires_grad and torch.is_grad_enabled():
+        if (points.requires_grad or rays.requires_grad) and torch.is_grad_enabled():
             from .segments import _SegmentTimes
 
+            flat = rays_c.reshape(-1, 6) if rays.requires_grad else rays_c.detach().reshape(-1, 6)
             seg["t_enter"], seg["t_exit"] = _SegmentTimes.apply(
-                points, rays_c.detach().reshape(-1, 6), seg["offsets"], seg["cells"], exit_cells, seg["t_enter"],
-                seg["t_exit"])
+                points, flat, seg["offsets"], seg["cells"], exit_cells, seg["t_enter"], seg["t_exit"])
         return seg
 
     def build_adjacent_diff(self, points, point_adjacency, point_adjacency_offsets):

@@ -3,9 +3,10 @@ any per-cell density and colour it can compute with autograd -- is rendered alon
 
 ``composite_segments`` has no kernel of its own: a handful of elementwise operations, one cumulative sum and two
 scatter-adds over the [S] entries.  It reads ``t_enter`` / ``t_exit`` with ordinary torch operations, so when those two
-carry a ``grad_fn`` with respect to the points (``Pipeline.trace_differentiable_segments``) everything composited from
-them is differentiable in the geometry.  The backward operator behind that is ``segment_points_grad``: a HIP kernel
-(rf_segments_grad.hip) on the device, a vectorised torch restatement of the same definition elsewhere.
+carry a ``grad_fn`` with respect to the points or the rays (``Pipeline.trace_differentiable_segments``) everything
+composited from them is differentiable in the geometry and in the camera.  The backward operators behind that are
+``segment_points_grad`` and ``segment_rays_grad``: HIP kernels (rf_segments_grad.hip, rf_segments_rays_grad.hip) on the
+device, vectorised torch restatements of the same definitions elsewhere.
 """
 from __future__ import annotations
 
@@ -85,12 +86,9 @@ def _check_segment_grad_inputs(seg, exit_cells, points, rays, grad_t_enter, grad
     return num_rays, total
 
 
-def _segment_points_grad_torch(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, num_rays, total):
-    """DESIGN 4.9, restated with torch operations over all S entries at once, in the dtype of ``points``."""
-    dev, dtype = points.device, points.dtype
-    out = torch.zeros_like(points)
-    if total == 0:
-        return out
+def _segment_face_totals(seg, exit_cells, dev, dtype, grad_t_enter, grad_t_exit, num_rays, total):
+    """What both restatements share: per entry the ray index, the cell, the cell behind its face (0 where
+    there is none), whether there is one, and the holder-aware total G, in ``dtype`` on ``dev``."""
     offsets = seg["offsets"].to(dev)
     cells = seg["cells"].to(dev).to(torch.int64)
     t_enter, t_exit = seg["t_enter"].to(dev), seg["t_exit"].to(dev)      # holders: from the stored floats
@@ -111,13 +109,24 @@ def _segment_points_grad_torch(seg, exit_cells, points, rays, grad_t_enter, grad
     held_by = torch.cat([latest.new_full((1,), -1), latest[:-1]])
     owned = held_by >= offsets[:-1][ray]
     total_grad = g_exit.index_add(0, held_by.clamp_min(0), torch.where(owned, g_enter, torch.zeros_like(g_enter)))
+    return ray, cells, torch.where(has_next, after, torch.zeros_like(after)), has_next, total_grad
+
+
+def _segment_points_grad_torch(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, num_rays, total):
+    """DESIGN 4.9, restated with torch operations over all S entries at once, in the dtype of ``points``."""
+    dev, dtype = points.device, points.dtype
+    out = torch.zeros_like(points)
+    if total == 0:
+        return out
+    ray, cells, after, has_next, total_grad = _segment_face_totals(
+        seg, exit_cells, dev, dtype, grad_t_enter, grad_t_exit, num_rays, total)
 
     live = has_next & (total_grad != 0)                                   # G == 0 exactly adds nothing: no 0 * inf
     r = rays.to(dev).reshape(-1, 6).to(dtype)
     origin = r[:, :3][ray]
     direction = (r[:, 3:] / (r[:, 3:] * r[:, 3:]).sum(-1, keepdim=True).sqrt())[ray]
     pa = points.detach()[cells]
-    pb = points.detach()[torch.where(has_next, after, torch.zeros_like(after))]
+    pb = points.detach()[after]
     normal = pb - pa
     num = (((pa + pb) / 2 - origin) * normal).sum(-1, keepdim=True)
     dp = (normal * direction).sum(-1, keepdim=True)
@@ -128,7 +137,34 @@ def _segment_points_grad_torch(seg, exit_cells, points, rays, grad_t_enter, grad
     grad_a = torch.where(live, weight * ((num * direction + dp * (origin - pa)) / den), zero)
     grad_b = torch.where(live, weight * (-(num * direction + dp * (origin - pb)) / den), zero)
     out.index_add_(0, cells, grad_a)
-    out.index_add_(0, torch.where(has_next, after, torch.zeros_like(after)), grad_b)
+    out.index_add_(0, after, grad_b)
+    return out
+
+
+def _segment_rays_grad_torch(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, num_rays, total):
+    """DESIGN 4.10, restated with torch operations over all S entries at once, in the dtype of ``points``."""
+    dev, dtype = points.device, points.dtype
+    out = torch.zeros((num_rays, 6), dtype=dtype, device=dev)
+    if total == 0:
+        return out
+    ray, cells, after, has_next, total_grad = _segment_face_totals(
+        seg, exit_cells, dev, dtype, grad_t_enter, grad_t_exit, num_rays, total)
+
+    live = (has_next & (total_grad != 0)).unsqueeze(-1)                   # G == 0 exactly adds nothing: no 0 * inf
+    r = rays.detach().to(dev).reshape(-1, 6).to(dtype)
+    length = (r[:, 3:] * r[:, 3:]).sum(-1, keepdim=True).sqrt()
+    origin = r[:, :3][ray]
+    direction = (r[:, 3:] / length)[ray]
+    pa = points.detach()[cells]
+    pb = points.detach()[after]
+    normal = pb - pa
+    num = (((pa + pb) / 2 - origin) * normal).sum(-1, keepdim=True)
+    dp = (normal * direction).sum(-1, keepdim=True)
+    weight = total_grad.unsqueeze(-1)
+    to_origin = -(weight / dp) * normal
+    to_direction = -(weight * num / (dp * dp * length[ray])) * (normal - dp * direction)
+    both = torch.cat([to_origin, to_direction], dim=-1)
+    out.index_add_(0, ray, torch.where(live, both, torch.zeros_like(both)))
     return out
 
 
@@ -144,8 +180,8 @@ def segment_points_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit
 
     with t the crossing of the ray (origin, normalised direction) and the exact bisector of (p_a, p_b) -- the
     derivative ``trace_backward`` uses, not that of the fp16 face table the walk ran on.  The gradient of t_enter in
-    front of a ray's first holder is dropped (t_enter is the constant 0 there).  Rays get no gradient; a grazing face
-    may give non-finite values, as in ``trace_backward``.
+    front of a ray's first holder is dropped (t_enter is the constant 0 there).  The rays' gradient is
+    ``segment_rays_grad``'s; a grazing face may give non-finite values, as in ``trace_backward``.
 
     CUDA tensors go through the HIP kernel (float32 points; one lane per entry, atomics into a zeroed [N, 3]).  CPU
     tensors, and CUDA tensors with ``backend="torch"``, go through a vectorised torch restatement in the dtype of
@@ -158,14 +194,20 @@ def segment_points_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit
     if backend == "torch":
         return _segment_points_grad_torch(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, num_rays, total)
 
+    if not points.is_cuda or points.dtype != torch.float32:
+        raise RuntimeError("the kernel takes float32 CUDA points (backend='torch' restates it for anything else)")
+    out = torch.zeros((points.size(0), 3), dtype=torch.float32, device=points.device)
+    return _segment_grad_hip("rf_segments_points_grad", out, seg, exit_cells, points, rays, grad_t_enter, grad_t_exit,
+                             num_rays, total)
+
+
+def _segment_grad_hip(symbol, out, seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, num_rays, total):
+    """The launch both gradient kernels share: ``symbol`` accumulates into the zeroed ``out``."""
     from . import _lib
     from .pipeline import _ptr, _stream_ptr
 
-    if not points.is_cuda or points.dtype != torch.float32:
-        raise RuntimeError("the kernel takes float32 CUDA points (backend='torch' restates it for anything else)")
     dev = points.device
-    out = torch.zeros((points.size(0), 3), dtype=torch.float32, device=dev)
-    if total == 0 or points.size(0) == 0:
+    if total == 0 or points.size(0) == 0 or num_rays == 0:
         return out
     if num_rays >= 2 ** 31:
         raise RuntimeError("too many rays for an int32 ray index")
@@ -185,7 +227,7 @@ def segment_points_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit
     counts = offsets[1:] - offsets[:-1]
     entry_ray = torch.repeat_interleave(torch.arange(num_rays, dtype=torch.int32, device=dev), counts, output_size=total)
     with torch.cuda.device(dev):
-        rc = _lib.load().rf_segments_points_grad(
+        rc = getattr(_lib.load(), symbol)(
             points_c.size(0), _ptr(points_c), num_rays, _ptr(rays_c), _ptr(offsets), total, _ptr(entry_ray),
             _ptr(cells), _ptr(t_enter), _ptr(t_exit), _ptr(exits), _ptr(g_enter), _ptr(g_exit), _ptr(out),
             _stream_ptr(dev))
@@ -193,9 +235,40 @@ def segment_points_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit
     return out
 
 
+def segment_rays_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, backend=None) -> torch.Tensor:
+    """dL/drays [R, 6] from dL/dt_enter [S] and dL/dt_exit [S] of the walk ``seg``: the other half of what the stored
+    times depend on (arguments of ``segment_points_grad``).  DESIGN 4.10, in the terms of 4.9 (a = cells[j], b = the
+    next cell, G_j the holder-aware total) and with n = p_b - p_a, m = (p_a + p_b) / 2, O the origin, D the stored
+    direction, d = D / |D|, num = (m - O) . n, dp = n . d:
+
+        ray_grad[r, 0:3] = sum over the ray's entries of G_j * (-n / dp)
+        ray_grad[r, 3:6] = sum over the ray's entries of G_j * (-num / (dp^2 |D|)) * (n - dp d)
+
+    the derivative of the crossing t = num / dp of the exact fp32 bisector with the cell sequence and the start cell
+    held fixed.  The second line has no component along D (scaling D changes nothing).  Faces with G_j == 0 exactly, or
+    without a next cell, add nothing; there is no guard beyond that: dp = 0 gives non-finite values in that ray's row.
+
+    CUDA tensors go through the HIP kernel (float32 points; one lane per entry, a segmented reduction in double within
+    the wave, one atomic update of a ray's row per wave the ray reaches into).  CPU tensors, and CUDA tensors with
+    ``backend="torch"``, go through a vectorised torch restatement in the dtype of ``points`` (float32 or float64): no
+    Python loop over rays."""
+    if backend not in (None, "hip", "torch"):
+        raise ValueError("backend must be None, 'hip' or 'torch'")
+    num_rays, total = _check_segment_grad_inputs(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit)
+    if backend is None:
+        backend = "hip" if points.is_cuda else "torch"
+    if backend == "torch":
+        return _segment_rays_grad_torch(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, num_rays, total)
+    if not points.is_cuda or points.dtype != torch.float32:
+        raise RuntimeError("the kernel takes float32 CUDA points (backend='torch' restates it for anything else)")
+    out = torch.zeros((num_rays, 6), dtype=torch.float32, device=points.device)
+    return _segment_grad_hip("rf_segments_rays_grad", out, seg, exit_cells, points, rays, grad_t_enter, grad_t_exit,
+                             num_rays, total)
+
+
 class _SegmentTimes(torch.autograd.Function):
-    """t_enter / t_exit of a walk as functions of the points: the forward hands back the stored tensors, the backward
-    is ``segment_points_grad``."""
+    """t_enter / t_exit of a walk as functions of the points and the rays: the forward hands back the stored tensors,
+    the backward is ``segment_points_grad`` and ``segment_rays_grad``, each only where its input needs a gradient."""
 
     @staticmethod
     def forward(ctx, points, rays, offsets, cells, exit_cells, t_enter, t_exit):
@@ -208,5 +281,10 @@ class _SegmentTimes(torch.autograd.Function):
         seg = {"offsets": offsets, "cells": cells, "t_enter": t_enter, "t_exit": t_exit}
         grad_t_enter = torch.zeros_like(t_enter) if grad_t_enter is None else grad_t_enter
         grad_t_exit = torch.zeros_like(t_exit) if grad_t_exit is None else grad_t_exit
-        grad = segment_points_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit)
-        return grad.to(points.dtype), None, None, None, None, None, None
+        grad_points = grad_rays = None
+        if ctx.needs_input_grad[0]:
+            grad_points = segment_points_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit).to(points.dtype)
+        if ctx.needs_input_grad[1]:
+            grad_rays = segment_rays_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit)
+            grad_rays = grad_rays.to(rays.dtype).reshape(rays.shape)
+        return grad_points, grad_rays, None, None, None, None, None
