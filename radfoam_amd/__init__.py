@@ -10,7 +10,7 @@ package ``radfoam/`` at the repo root.
 from .geometry import CellGeometry, cell_geometry, cell_surface
 from .pipeline import Pipeline, create_pipeline, invalidate_caches
 from .scene_ops import pack_attributes
-from .segments import composite_segments, segment_points_grad, segment_rays_grad
+from .segments import composite_entries, composite_segments, segment_points_grad, segment_rays_grad
 from .shims import (BatchFetcher, Triangulation, TriangulationFailedError, Viewer, build_aabb_tree,
                     farthest_neighbor, nn, run_with_viewer)
 
@@ -18,5 +18,5 @@ __all__ = [
     "Pipeline", "create_pipeline", "Triangulation", "TriangulationFailedError", "build_aabb_tree",
     "nn", "farthest_neighbor", "BatchFetcher", "Viewer", "run_with_viewer", "pack_attributes",
     "invalidate_caches", "CellGeometry", "cell_geometry", "cell_surface", "composite_segments",
-    "segment_points_grad", "segment_rays_grad",
+    "segment_points_grad", "segment_rays_grad", "composite_entries",
 ]

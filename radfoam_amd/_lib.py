@@ -64,7 +64,8 @@ class LaunchOpts(C.Structure):
     ]
 
 
-# every symbol include/radfoam_hip.h, radfoam_hip_geometry.h and radfoam_hip_segments.h declare: name -> (restype, argtypes)
+# every symbol include/radfoam_hip.h, radfoam_hip_geometry.h, radfoam_hip_segments.h and radfoam_hip_composite.h declare:
+# name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
 _INT = C.c_int
@@ -123,6 +124,9 @@ SYMBOLS = {
     "rf_trace_segments_exit_cells": (_INT, [_U32, _U32, _P, _U32, _P, _P, _P, _P, _P, _P]),
     "rf_segments_points_grad": (_INT, [_U32, _P, _U32, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rf_segments_rays_grad": (_INT, [_U32, _P, _U32, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rf_composite_rays_per_wave": (_U32, []),
+    "rf_composite_entries_forward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _U32, _P, _P]),
+    "rf_composite_entries_backward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -7,6 +7,9 @@ carry a ``grad_fn`` with respect to the points or the rays (``Pipeline.trace_dif
 composited from them is differentiable in the geometry and in the camera.  The backward operators behind that are
 ``segment_points_grad`` and ``segment_rays_grad``: HIP kernels (rf_segments_grad.hip, rf_segments_rays_grad.hip) on the
 device, vectorised torch restatements of the same definitions elsewhere.
+
+``composite_entries`` is the same compositing for inputs the caller has per ENTRY (a density [S] and any number of
+channels [S, C]), with kernels of its own for float32 tensors on the device (rf_composite.hip).
 """
 from __future__ import annotations
 
@@ -61,6 +64,140 @@ def composite_segments(seg, density: torch.Tensor, rgb: torch.Tensor) -> torch.T
     colour = out[:, :3].index_add(0, ray, weight.unsqueeze(-1) * rgb[cells].to(torch.float64))
     alpha = -torch.expm1(run0[offsets[1:]] - before)
     return torch.cat([colour, alpha.unsqueeze(-1)], dim=-1).to(dtype)
+
+
+def _check_entries_inputs(seg, sigma, values):
+    if sigma.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("sigma must have float32 or float64 dtype")
+    if values.dtype != sigma.dtype or values.device != sigma.device:
+        raise RuntimeError("values must have the dtype and device of sigma")
+    if sigma.dim() != 1 or values.dim() != 2 or values.size(-1) < 1:
+        raise RuntimeError("expected sigma [S] and values [S, C] with C >= 1")
+    offsets = seg["offsets"]
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise RuntimeError("seg['offsets'] must be int64 [R+1]")
+    total = sigma.size(0)
+    if seg["t_enter"].numel() != total or seg["t_exit"].numel() != total or values.size(0) != total:
+        raise RuntimeError("sigma, values, seg['t_enter'] and seg['t_exit'] must have one element (row) per entry")
+    return offsets.numel() - 1, total
+
+
+def _composite_entries_torch(offsets, t_enter, t_exit, sigma, values):
+    """The definition with the operations of ``composite_segments``: float64 throughout, a segmented exclusive
+    cumulative sum for the transmittance, one ``index_add`` over the ray index.  Autograd differentiates it."""
+    dev, dtype = sigma.device, sigma.dtype
+    num_rays, total = offsets.numel() - 1, sigma.size(0)
+    t_enter = t_enter.to(dev).to(torch.float64).reshape(-1)
+    t_exit = t_exit.to(dev).to(torch.float64).reshape(-1)
+    dt = torch.where(torch.isinf(t_exit), torch.zeros_like(t_exit), (t_exit - t_enter).clamp_min(0.0))
+
+    log_keep = -sigma.to(torch.float64) * dt                       # -x of every entry
+    run = torch.cumsum(log_keep, 0)                                # inclusive, across ray boundaries
+    run0 = torch.cat([run.new_zeros(1), run])                      # run0[e] = sum of the entries before e
+    counts = offsets[1:] - offsets[:-1]
+    ray = torch.repeat_interleave(torch.arange(num_rays, device=dev), counts, output_size=total)
+    before = run0[offsets[:-1]]                                    # [R]: the sum in front of each ray's first entry
+    transmittance = torch.exp(run0[:-1] - before[ray])             # in front of every entry, within its ray
+    weight = transmittance * -torch.expm1(log_keep)
+
+    out = torch.zeros((num_rays, values.size(1)), dtype=torch.float64, device=dev)
+    composited = out.index_add(0, ray, weight.unsqueeze(-1) * values.to(torch.float64))
+    alpha = -torch.expm1(run0[offsets[1:]] - before)
+    return torch.cat([composited, alpha.unsqueeze(-1)], dim=-1).to(dtype)
+
+
+class _CompositeEntries(torch.autograd.Function):
+    """``composite_entries`` through the kernels of rf_composite.hip: float32 CUDA tensors, each gradient only where
+    its input needs one.  Nothing but the inputs is kept for the backward, which sweeps the list again."""
+
+    @staticmethod
+    def forward(ctx, sigma, values, t_enter, t_exit, offsets):
+        from . import _lib
+        from .pipeline import _ptr, _stream_ptr
+
+        dev = sigma.device
+        num_rays, total, channels = offsets.numel() - 1, sigma.size(0), values.size(1)
+        if num_rays >= 2 ** 31 or channels >= 2 ** 31:
+            raise RuntimeError("too many rays or channels for the kernel")
+        offsets = offsets.to(dev).contiguous()
+        sigma_c, values_c = sigma.detach().contiguous(), values.detach().contiguous()
+        t_enter_c = t_enter.detach().to(dev).to(torch.float32).reshape(-1).contiguous()
+        t_exit_c = t_exit.detach().to(dev).to(torch.float32).reshape(-1).contiguous()
+        ctx.save_for_backward(sigma_c, values_c, t_enter_c, t_exit_c, offsets)
+        ctx.times = tuple((t.dtype, t.device, t.shape) for t in (t_enter, t_exit))
+        if num_rays == 0 or total == 0:
+            return torch.zeros((num_rays, channels + 1), dtype=torch.float32, device=dev)
+        out = torch.empty((num_rays, channels + 1), dtype=torch.float32, device=dev)     # every element is written
+        with torch.cuda.device(dev):
+            rc = _lib.load().rf_composite_entries_forward(
+                num_rays, _ptr(offsets), total, _ptr(t_enter_c), _ptr(t_exit_c), _ptr(sigma_c), _ptr(values_c),
+                channels, _ptr(out), _stream_ptr(dev))
+        _lib.check(rc)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import _lib
+        from .pipeline import _ptr, _stream_ptr
+
+        sigma, values, t_enter, t_exit, offsets = ctx.saved_tensors
+        dev = sigma.device
+        num_rays, total, channels = offsets.numel() - 1, sigma.size(0), values.size(1)
+        want = ctx.needs_input_grad[:4]
+        # entries outside offsets[0] .. offsets[R] are not written by the kernel: there are none in a sound list
+        grads = [torch.empty_like(t) if w else None for t, w in zip((sigma, values, t_enter, t_exit), want)]
+        if num_rays > 0 and total > 0 and any(want):
+            grad_out = grad_out.to(torch.float32).contiguous()
+            with torch.cuda.device(dev):
+                rc = _lib.load().rf_composite_entries_backward(
+                    num_rays, _ptr(offsets), total, _ptr(t_enter), _ptr(t_exit), _ptr(sigma), _ptr(values), channels,
+                    _ptr(grad_out), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _stream_ptr(dev))
+            _lib.check(rc)
+        for i, (dtype, device, shape) in zip((2, 3), ctx.times):
+            if grads[i] is not None:
+                grads[i] = grads[i].to(device).to(dtype).reshape(shape)
+        return grads[0], grads[1], grads[2], grads[3], None
+
+
+def composite_entries(seg, sigma: torch.Tensor, values: torch.Tensor, backend=None) -> torch.Tensor:
+    """[R, C+1] for the rays of ``seg`` (the dict ``Pipeline.trace_segments`` or ``trace_differentiable_segments``
+    returns; ``offsets`` int64 [R+1] and ``t_enter`` / ``t_exit`` [S] are read, ``cells`` is not) from values the caller
+    has PER ENTRY: ``sigma`` [S] and ``values`` [S, C], C >= 1, of one dtype (float32 or float64) and device.  Per ray,
+    over its entries in order (the compositing of ``composite_segments``):
+
+        dt = 0 where t_exit is infinite, else max(t_exit - t_enter, 0),      x = sigma dt
+        T = exp(-(sum of x over the ray's earlier entries)),      w = T (1 - exp(-x))
+        out[r, c] = sum of w values[:, c],      out[r, C] = 1 - exp(-(sum of x))
+
+    Channels 0 .. C-1 are the composited values, channel C is the opacity; a ray without entries gives a row of zeros;
+    the result has the dtype of ``sigma``.  ``composite_entries(seg, density[cells], rgb[cells])`` is
+    ``composite_segments(seg, density, rgb)``; what this adds is everything a per-cell table cannot hold: a colour that
+    depends on the ray (examples/view_dependent_shading.py), more than three channels, a density of the entry.
+
+    Differentiable in ``sigma``, ``values``, ``seg["t_enter"]`` and ``seg["t_exit"]`` (which carry the gradient on to
+    the points and the rays when they come from ``trace_differentiable_segments``).  The times' gradient follows
+    torch's ``clamp_min``: an entry with t_exit >= t_enter, both finite, passes it on, t_exit < t_enter does not, and
+    an entry with an infinite t_exit gets exact zeros in every gradient.
+
+    ``backend``: None, "hip" or "torch".  None is "hip" for float32 CUDA ``sigma`` and "torch" for everything else.
+    "hip" runs the kernels of rf_composite.hip (one wave owns a run of consecutive rays, sums in double, one rounding
+    to float32, no atomics: the same bits from call to call, gradients included; the times are read as float32).
+    "torch" is a vectorised restatement with ``composite_segments``' float64 segmented cumulative sum, differentiated by
+    autograd, on any device; no Python loop over rays.  ``offsets[-1] == S`` is checked on the torch path only, and
+    there only when ``seg["offsets"]`` lives on the CPU: on the device the check would be a synchronisation the caller
+    has not asked for.  (The kernels clamp every offset to 0 .. S instead.)"""
+    if backend not in (None, "hip", "torch"):
+        raise ValueError("backend must be None, 'hip' or 'torch'")
+    num_rays, total = _check_entries_inputs(seg, sigma, values)
+    if backend is None:
+        backend = "hip" if sigma.is_cuda and sigma.dtype == torch.float32 else "torch"
+    if backend == "torch":
+        if not seg["offsets"].is_cuda and int(seg["offsets"][-1]) != total:
+            raise RuntimeError("seg['offsets'][-1] must be the number of entries")
+        return _composite_entries_torch(seg["offsets"].to(sigma.device), seg["t_enter"], seg["t_exit"], sigma, values)
+    if not sigma.is_cuda or sigma.dtype != torch.float32:
+        raise RuntimeError("the kernel takes float32 CUDA sigma and values (backend='torch' restates it for anything else)")
+    return _CompositeEntries.apply(sigma, values, seg["t_enter"], seg["t_exit"], seg["offsets"])
 
 
 _NONE = 0xFFFFFFFF
