@@ -114,3 +114,177 @@ def test_face_polygons_are_wound_from_a_to_b():
         poly = H.face_polygon(c["points"], c["adjacency"], c["offsets"], a, int(e))
         normal = np.cross(poly[1:-1] - poly[0], poly[2:] - poly[0])
         assert (normal @ (pts[b] - pts[a]) > 0).all()
+
+
+# ---- the exact reference (tests/cell_geometry_ref.py) and the clouds that stand on the kernel's seams --------------------
+#
+# Worst ratios of the host build against the exact reference, in units of each cell's own size (bar 1e-9):
+#   ring16/17 |dV| 1e-14, ring256 |dV| 9e-14 |dc| 2e-13 |dA| 2e-13, hub64/65/200 |dV| 2e-14 |dA| 1e-13,
+#   uniform400 / scaled_* |dV| 1e-14, offset |dc| 2e-13, redo_spread |dV| 1e-14 |dA| 8e-14, grid |dV| 2e-15,
+#   clustered |dV| 1.2e-10 |dc| 4.4e-11 |dA| 2.9e-10 symmetry 4.2e-10 closure 4.3e-10 (R = 4 |diagonal| is 1e6 times its
+#   smallest cells; still under the bar, so no Qhull yardstick was needed).
+
+from fractions import Fraction
+
+from tests import cell_geometry_ref as X
+
+EXACT_CASES = ["ring16", "ring17", "ring256", "hub64", "hub65", "hub200", "redo_spread", "clustered", "uniform400",
+               "offset", "scaled_small", "scaled_large"]
+_HOST = {}
+
+
+def _host(name, cap=256):
+    if (name, cap) not in _HOST:
+        c = H.case(name)
+        _HOST[(name, cap)] = H.cell_geometry(c["points"], c["adjacency"], c["offsets"], cap=cap)
+    return _HOST[(name, cap)]
+
+
+def test_exact_reference_returns_the_closed_form_on_a_grid():
+    c = H.case("grid")
+    ex, h = c["exact"], Fraction(1, 4)
+    inner = H.grid_interior()
+    assert inner.sum() == 64 and np.array_equal(~ex["open"], inner)
+    pts = c["points"]
+    for a in np.nonzero(inner)[0]:
+        assert ex["volume"][a] == h ** 3
+        assert ex["centroid"][a] == tuple(Fraction(float(x)) for x in pts[a])
+        lo, hi = int(c["offsets"][a]), int(c["offsets"][a + 1])
+        areas = c["slots"]["area"][lo:hi]
+        axis = np.abs(pts[c["adjacency"][lo:hi]] - pts[a]).sum(1) == 0.25
+        assert axis.sum() == 6 and (areas[axis] == 0.0625).all() and (areas[~axis] == 0.0).all()
+    assert (c["slots"]["area"][inner[c["rows"]]] == 0.0).sum() > 0        # the triangulated adjacency lists diagonals
+
+
+@pytest.mark.parametrize("k", [16, 17, 256, 257])
+def test_ring_clouds_share_a_k_gon_that_never_needs_more_room(k):
+    c = H.case(f"ring{k}")
+    ex = c["exact"]
+    assert not ex["open"][:k + 2].any() and ex["open"][k + 2:].all()           # axis and ring cells bounded: k + 2
+    assert ex["faces"][(0, 1)][1] == k
+    assert (ex["extent"][:k + 2] < 0.5 * c["R"]).all()
+    if k == 16:     # the axis cells stay on the lane path: no face of theirs has more than kLaneCap vertices
+        for a in (0, 1):
+            assert c["slots"]["vertices"][int(c["offsets"][a]):int(c["offsets"][a + 1])].max() == 16
+    assert (_host(f"ring{k}", cap=k)["status"][:2] == 0).all()
+    assert (_host(f"ring{k}", cap=k - 1)["status"][:2] == 1).all()
+    got = _host(f"ring{k}", cap=k)
+    assert got["face_vertices"][H.slot_of(c, 0, 1)] == k == got["face_vertices"][H.slot_of(c, 1, 0)]
+
+
+@pytest.mark.parametrize("k", [64, 65, 200])
+def test_hub_clouds_give_the_centre_a_row_of_exactly_k(k):
+    c = H.case(f"hub{k}")
+    ex = c["exact"]
+    assert int(c["offsets"][1]) - int(c["offsets"][0]) == k
+    assert np.array_equal(c["adjacency"][:k], np.arange(1, k + 1))
+    assert not ex["open"][:k + 1].any() and (ex["extent"][:k + 1] < 0.5 * c["R"]).all()
+    assert (c["slots"]["vertices"][:k] >= 3).all()
+
+
+def test_redo_spread_puts_17_gons_in_three_blocks_of_the_redo_kernel():
+    c = H.case("redo_spread")
+    blocks = [a // 64 for a, _ in H.REDO_SPREAD_PAIRS]
+    assert blocks == [b // 64 for _, b in H.REDO_SPREAD_PAIRS] == [0, 0, 1, 3]
+    for a, b in H.REDO_SPREAD_PAIRS:
+        assert c["exact"]["faces"][(a, b)][1] == 17 and not c["exact"]["open"][[a, b]].any()
+    assert not c["exact"]["open"][:74].any()
+
+
+def test_the_other_clouds_are_what_they_claim():
+    c = H.case("clustered")
+    size = np.cbrt(c["exact"]["volume_f"][~c["exact"]["open"]])
+    assert len(c["points"]) == 600 and (~c["exact"]["open"]).sum() >= 500 and size.max() / size.min() > 1e4
+    base = H.case("uniform400")
+    assert (~base["exact"]["open"]).sum() >= 300
+    for name, f in (("scaled_small", 2.0 ** -10), ("scaled_large", 2.0 ** 10)):
+        s = H.case(name)
+        assert np.array_equal(s["points"].astype(np.float64), base["points"].astype(np.float64) * f)
+        assert np.array_equal(s["adjacency"], base["adjacency"]) and np.array_equal(s["offsets"], base["offsets"])
+        # the reference says exactly how the outputs scale
+        assert all(v == w * Fraction(f) ** 3 for v, w in zip(s["exact"]["volume"], base["exact"]["volume"])
+                   if w is not None)
+    assert (~H.case("offset")["exact"]["open"]).sum() >= 300
+    assert np.abs(H.case("offset")["points"]).min(0).tolist() > [900.0, 1900.0, 400.0]
+
+
+@pytest.mark.parametrize("name", EXACT_CASES)
+def test_clipping_core_on_the_host_matches_the_exact_reference(name):
+    share = None if name == "clustered" else 0.05
+    H.check_against_exact(H.case(name), _host(name), share=share)
+
+
+def test_257_vertices_are_reported_and_every_other_cell_is_untouched():
+    c = H.case("ring257")
+    got, full = _host("ring257"), _host("ring257", cap=300)
+    assert (got["status"][:2] == 1).all() and (got["status"][2:] == 0).all() and got["bad"] == 2
+    assert np.isnan(got["volume"][:2]).all() and not got["bounded"][:2].any()
+    ok = got["status"] == 0
+    for key in ("volume", "centroid", "bounded"):
+        assert np.array_equal(got[key][ok], full[key][ok], equal_nan=True)
+    of_ok = ok[c["rows"]]
+    assert np.array_equal(got["face_area"][of_ok], full["face_area"][of_ok])
+    H.check_against_exact(c, full)                       # and with room for it the 257-gon is right
+
+
+@pytest.mark.parametrize("k", [64, 65, 200])
+def test_hub_centre_on_the_host(k):
+    c, got = H.case(f"hub{k}"), _host(f"hub{k}")
+    assert np.isfinite(got["face_area"][:k]).all() and (got["face_area"][:k] > 0).all()
+    assert np.array_equal(got["face_vertices"][:k].astype(np.int64), c["slots"]["vertices"][:k])
+    H.check_against_exact(c, got, cells=np.arange(k + 1))
+
+
+def test_power_of_two_scaling_commutes_bit_for_bit_on_the_host():
+    base = _host("uniform400")
+    for name, f in (("scaled_small", 2.0 ** -10), ("scaled_large", 2.0 ** 10)):
+        got = _host(name)
+        assert np.array_equal(got["volume"], base["volume"] * f ** 3)
+        assert np.array_equal(got["centroid"], base["centroid"] * f, equal_nan=True)
+        assert np.array_equal(got["face_area"], base["face_area"] * f ** 2)
+
+
+def test_grid_of_cospherical_sites_on_the_host():
+    c, got = H.case("grid"), _host("grid")
+    assert got["bad"] == 0
+    H.check_grid(c, got)
+    H.check_against_exact(c, got, vertices=False)
+
+
+def test_tiny_inputs_on_the_host():
+    tiny = H.tiny_inputs()
+    got = H.cell_geometry(*[tiny["n4"][i] for i in (0, 2, 1)])
+    assert got["bad"] == 0 and not got["bounded"].any() and np.isposinf(got["volume"]).all()
+    assert np.isnan(got["centroid"]).all() and np.isposinf(got["face_area"]).all()
+    for name in ("n1", "n2"):
+        got = H.cell_geometry(*[tiny[name][i] for i in (0, 2, 1)])
+        assert got["bad"] == 0 and not got["bounded"].any() and np.isposinf(got["volume"]).all()
+    a = H.EMPTY_ROW_SITE
+    full = H.cell_geometry(*[tiny["empty_row_full"][i] for i in (0, 2, 1)])
+    got = H.cell_geometry(*[tiny["empty_row"][i] for i in (0, 2, 1)])
+    assert full["bounded"][a] and full["bounded"].sum() > 5
+    assert got["bad"] == 0 and not got["bounded"][a] and np.isposinf(got["volume"][a]) and np.isnan(got["centroid"][a]).all()
+    rest = np.arange(len(full["volume"])) != a
+    for key in ("volume", "centroid", "bounded"):
+        assert np.array_equal(got[key][rest], full[key][rest], equal_nan=True)
+
+
+def test_surfaces_on_the_host():
+    c = H.case("hub200")
+    inside = np.zeros(len(c["points"]), dtype=bool)
+    inside[0] = True
+    tri, edge = H.host_surface(c, inside)
+    assert len(edge) == (c["slots"]["vertices"][:200] - 2).sum()
+    H.check_surface(c, inside, tri, edge, c["exact"]["volume_f"][0], np.cbrt(c["exact"]["volume_f"][0]))
+    c = H.case("grid")
+    block = np.zeros((6, 6, 6), dtype=bool)
+    block[2:4, 2:4, 2:4] = True
+    tri, edge = H.host_surface(c, block.reshape(-1))
+    H.check_surface(c, block.reshape(-1), tri, edge, 8 * H.GRID_H ** 3, H.GRID_H, area=24 * H.GRID_H ** 2,
+                    counts=False)      # zero-area faces of cospherical sites have whatever count they have
+    c = H.case("ring17")
+    inside = np.zeros(len(c["points"]), dtype=bool)
+    inside[1] = True
+    tri, edge = H.host_surface(c, inside)
+    assert (edge == H.slot_of(c, 1, 0)).sum() == 15
+    H.check_surface(c, inside, tri, edge, c["exact"]["volume_f"][1], np.cbrt(c["exact"]["volume_f"][1]))

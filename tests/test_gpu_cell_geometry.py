@@ -144,3 +144,149 @@ def test_the_gpu_triangulation_feeds_straight_in():
     diff = np.abs(volume[was] - t["np"]["volume"][was]).max()
     print(f"triangulation CSR: max |dV| = {diff / c['h'] ** 3:.3g} h^3")
     assert diff <= 1e-9 * c["h"] ** 3
+
+
+# ---- the kernel's seams, against the exact reference (tests/cell_geometry_ref.py) ----------------------------------------
+#
+# Bars are per cell, in units of its own size s_a = V_ref,a^(1/3): 1e-9 s_a^3 / s_a^2 / s_a (clip_host.check_cells /
+# check_faces with local=True).  The CPU twins in tests/test_cell_geometry.py assert the construction of every cloud.
+# Worst ratios measured on the MI355X (|dV| / s^3, |dc| / s, |dA| / s^2; the host build gives the same figures):
+#   ring16 3e-15 2e-15 1e-14, ring17 1e-14 4e-15 1e-14, ring256 9e-14 2e-13 2e-13, hub64/65 1e-14 4e-15 5e-14,
+#   hub200 2e-14 9e-15 1e-13, redo_spread 1.2e-14 8.7e-15 8.0e-14, uniform400 and both scalings 1.2e-14 4.9e-15 4.4e-14,
+#   offset 8.4e-15 2.0e-13 2.9e-14, grid 1.6e-15 6.7e-16 7e-15,
+#   clustered 1.2e-10 4.4e-11 2.9e-10 (symmetry 4.2e-10, closure 4.3e-10): R = 4 |diagonal| is about 1e6 of its smallest
+#   cells and the first clips of the square cost that much; still under 1e-9, so the bar was not widened and no Qhull
+#   yardstick was needed.  Either-way share: 0 % on the ring, hub, redo and grid clouds, 3.1 % on the 400-site clouds,
+#   1.4 % on clustered.  Both scalings equal the unscaled cloud times 2^+-30 / 2^+-20 / 2^+-10 bit for bit.
+
+def _device_tensors(points, offsets, adjacency):
+    dev = "cuda:0"
+    return (torch.from_numpy(points).to(dev), torch.from_numpy(adjacency.astype(np.int64)).to(dev).to(torch.uint32),
+            torch.from_numpy(offsets.astype(np.int64)).to(dev).to(torch.uint32))
+
+
+def _device_out(name):
+    """cell_geometry's answer plus face_vertices (the count cell_surface works from), as numpy"""
+    from radfoam_amd import geometry
+
+    t = _device_case(name)
+    if "out" not in t:
+        _, nv = geometry._run_geometry(*geometry._prepare(t["points"], t["adjacency"], t["offsets"]))
+        t["out"] = dict(t["np"], face_vertices=nv.cpu().numpy())
+    return t["out"]
+
+
+def _surface(name, inside):
+    import radfoam
+
+    t = _device_case(name)
+    tri, edge = radfoam.cell_surface(t["points"], t["adjacency"], t["offsets"], torch.from_numpy(inside).to("cuda:0"))
+    assert tri.dtype == torch.float64 and edge.dtype == torch.int64
+    return tri.cpu().numpy(), edge.cpu().numpy()
+
+
+@pytest.mark.parametrize("k", [16, 17, 256])
+def test_a_k_gon_at_the_capacity_of_the_lane_path_and_of_the_serial_path(k):
+    """16 vertices stay in the lane's LDS slot, 17 hand both axis cells on (and leave every other cell as it was), 256
+    fill the serial path."""
+    c, out = H.case(f"ring{k}"), _device_out(f"ring{k}")
+    assert out["face_vertices"][H.slot_of(c, 0, 1)] == k == out["face_vertices"][H.slot_of(c, 1, 0)]
+    H.check_against_exact(c, out, cells=np.array([0, 1]))
+    H.check_against_exact(c, out)
+
+
+def test_a_257_gon_raises_naming_an_axis_cell():
+    import radfoam
+    from radfoam_amd import foam
+
+    pts = H._CLOUDS["ring257"]()
+    off, adj = foam.delaunay_csr(pts)
+    with pytest.raises(RuntimeError, match=r"cell [01] is not supported: a face outgrew 256 vertices"):
+        radfoam.cell_geometry(*[_device_tensors(pts, off, adj)[i] for i in (0, 1, 2)])
+
+
+@pytest.mark.parametrize("k", [64, 65, 200])
+def test_a_row_of_64_faces_on_the_wave_path_and_longer_rows_on_the_serial_path(k):
+    c, out = H.case(f"hub{k}"), _device_out(f"hub{k}")
+    assert int(c["offsets"][1]) == k
+    assert np.isfinite(out["face_area"][:k]).all() and (out["face_area"][:k] > 0).all()
+    assert np.array_equal(out["face_vertices"][:k].astype(np.int64), c["slots"]["vertices"][:k])
+    H.check_against_exact(c, out, cells=np.arange(k + 1))
+    H.check_against_exact(c, out)
+
+
+def test_handed_on_cells_in_several_blocks_of_the_redo_kernel():
+    c, out = H.case("redo_spread"), _device_out("redo_spread")
+    pairs = np.array(H.REDO_SPREAD_PAIRS)
+    for a, b in pairs:
+        assert out["face_vertices"][H.slot_of(c, int(a), int(b))] == 17
+    H.check_against_exact(c, out, cells=pairs.reshape(-1))
+    in_blocks = np.isin(np.arange(len(c["points"])) // 64, pairs[:, 0] // 64) & ~c["exact"]["open"]
+    H.check_against_exact(c, out, cells=np.nonzero(in_blocks)[0])
+
+
+@pytest.mark.parametrize("name", ["clustered", "uniform400", "offset", "scaled_small", "scaled_large"])
+def test_cells_of_very_different_sizes_far_from_the_origin_and_scaled(name):
+    c, out = H.case(name), _device_out(name)
+    H.check_against_exact(c, out, share=None if name == "clustered" else 0.05)
+    if name.startswith("scaled"):       # a power of two commutes with every operation of rf_clip.hpp: bit for bit
+        f = 2.0 ** (-10 if name == "scaled_small" else 10)
+        base = _device_out("uniform400")
+        assert np.array_equal(out["volume"], base["volume"] * f ** 3)
+        assert np.array_equal(out["centroid"], base["centroid"] * f, equal_nan=True)
+        assert np.array_equal(out["face_area"], base["face_area"] * f ** 2)
+
+
+def test_a_grid_of_cospherical_sites():
+    c, out = H.case("grid"), _device_out("grid")
+    H.check_grid(c, out)
+    H.check_against_exact(c, out, vertices=False)
+
+
+def test_tiny_inputs():
+    import radfoam
+
+    tiny = H.tiny_inputs()
+    run = lambda name: radfoam.cell_geometry(*_device_tensors(*tiny[name]))
+    geo = run("n4")
+    assert not geo.bounded.any() and torch.isposinf(geo.volume).all() and torch.isnan(geo.centroid).all()
+    assert torch.isposinf(geo.face_area).all()
+    for name, n in (("n1", 1), ("n2", 2)):
+        geo = run(name)
+        assert geo.volume.shape == (n,) and geo.face_area.shape == (0,)
+        assert not geo.bounded.any() and torch.isposinf(geo.volume).all() and torch.isnan(geo.centroid).all()
+    a = H.EMPTY_ROW_SITE
+    full, got = run("empty_row_full"), run("empty_row")
+    assert bool(full.bounded[a]) and not bool(got.bounded[a])
+    assert torch.isposinf(got.volume[a]) and torch.isnan(got.centroid[a]).all()
+    rest = np.arange(full.volume.numel()) != a
+    for key in ("volume", "centroid", "bounded"):
+        assert np.array_equal(getattr(got, key).cpu().numpy()[rest], getattr(full, key).cpu().numpy()[rest],
+                              equal_nan=True)
+
+
+def test_surface_of_the_hub_of_200_faces():
+    c = H.case("hub200")
+    inside = np.zeros(len(c["points"]), dtype=bool)
+    inside[0] = True
+    tri, edge = _surface("hub200", inside)
+    assert len(edge) == (c["slots"]["vertices"][:200] - 2).sum()
+    H.check_surface(c, inside, tri, edge, c["exact"]["volume_f"][0], np.cbrt(c["exact"]["volume_f"][0]))
+
+
+def test_surface_of_a_block_of_grid_cells():
+    c = H.case("grid")
+    block = np.zeros((6, 6, 6), dtype=bool)
+    block[2:4, 2:4, 2:4] = True
+    tri, edge = _surface("grid", block.reshape(-1))
+    H.check_surface(c, block.reshape(-1), tri, edge, 8 * H.GRID_H ** 3, H.GRID_H, area=24 * H.GRID_H ** 2,
+                    counts=False)      # zero-area faces of cospherical sites have whatever count they have
+
+
+def test_surface_of_an_axis_cell_of_the_17_gon():
+    c = H.case("ring17")
+    inside = np.zeros(len(c["points"]), dtype=bool)
+    inside[1] = True
+    tri, edge = _surface("ring17", inside)
+    assert (edge == H.slot_of(c, 1, 0)).sum() == 15
+    H.check_surface(c, inside, tri, edge, c["exact"]["volume_f"][1], np.cbrt(c["exact"]["volume_f"][1]))
