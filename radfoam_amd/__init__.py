@@ -7,7 +7,7 @@ include/radfoam_hip.h; everything else the reference module exports is a torch/s
 (radfoam_amd/shims.py).  ``import radfoam`` resolves to this package through the alias
 package ``radfoam/`` at the repo root.
 """
-from .geometry import CellGeometry, cell_geometry, cell_surface
+from .geometry import CellGeometry, cell_geometry, cell_geometry_grad, cell_surface, differentiable_cell_geometry
 from .pipeline import Pipeline, create_pipeline, invalidate_caches
 from .scene_ops import pack_attributes
 from .segments import composite_entries, composite_segments, segment_points_grad, segment_rays_grad
@@ -18,5 +18,6 @@ __all__ = [
     "Pipeline", "create_pipeline", "Triangulation", "TriangulationFailedError", "build_aabb_tree",
     "nn", "farthest_neighbor", "BatchFetcher", "Viewer", "run_with_viewer", "pack_attributes",
     "invalidate_caches", "CellGeometry", "cell_geometry", "cell_surface", "composite_segments",
-    "segment_points_grad", "segment_rays_grad", "composite_entries",
+    "segment_points_grad", "segment_rays_grad", "composite_entries", "cell_geometry_grad",
+    "differentiable_cell_geometry",
 ]

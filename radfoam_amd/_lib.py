@@ -64,7 +64,8 @@ class LaunchOpts(C.Structure):
     ]
 
 
-# every symbol include/radfoam_hip.h, radfoam_hip_geometry.h, radfoam_hip_segments.h and radfoam_hip_composite.h declare:
+# every symbol include/radfoam_hip.h, radfoam_hip_geometry.h, radfoam_hip_geometry_grad.h, radfoam_hip_segments.h and
+# radfoam_hip_composite.h declare:
 # name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -117,6 +118,8 @@ SYMBOLS = {
                                   C.POINTER(Camera), _P, _P, C.POINTER(LaunchOpts), _P]),
     "rf_cell_geometry_workspace_bytes": (C.c_size_t, [_U32]),
     "rf_cell_geometry": (_INT, [_P, _U32, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "rf_cell_geometry_grad_workspace_bytes": (C.c_size_t, [_U32]),
+    "rf_cell_geometry_grad": (_INT, [_P, _U32, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "rf_cell_surface_count": (_INT, [_U32, _P, _P, _U32, _P, _P, _P, _P]),
     "rf_cell_surface_emit": (_INT, [_P, _U32, _P, _P, _U32, _P, _P, _P, _P, _U32, _P, _P, _P]),
     "rf_trace_segments_count": (_INT, [C.POINTER(TraceSettings), _U32, _U32, _P, _U32, _P, _P, _P, _P, _P]),

@@ -3,10 +3,12 @@
   cell_geometry   volume, centroid, boundedness of every cell and the area of every face, in double
   cell_surface    the faces between selected and unselected cells, as triangles: the foam's own watertight surface of
                   e.g. ``density > tau``
+  cell_geometry_grad            the gradient of a function of the volumes and centroids with respect to ``points``
+  differentiable_cell_geometry  cell_geometry whose volume and centroid carry autograd to ``points``
 
 Cell ``a`` is the intersection of the half-spaces of its row of ``point_adjacency`` (taken as given); no tetrahedra are
-involved.  Both take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip behind the C-ABI of
-include/radfoam_hip_geometry.h; there is no CPU path.
+involved.  All take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip and csrc/rf_cell_geometry_grad.hip
+behind the C-ABI of include/radfoam_hip_geometry.h and include/radfoam_hip_geometry_grad.h; there is no CPU path.
 """
 from __future__ import annotations
 
@@ -126,3 +128,84 @@ def cell_surface(points: torch.Tensor, point_adjacency: torch.Tensor, point_adja
                                             _ptr(slots), _ptr(begins), slots.numel(), _ptr(triangles), _ptr(edge),
                                             _stream(dev)))
     return triangles, edge
+
+
+def _upstream(name, t, shape, device):
+    if t is None:
+        return None
+    if not t.is_cuda or t.device != device or tuple(t.shape) != shape or not t.dtype.is_floating_point:
+        raise RuntimeError(f"{name} must be a floating-point CUDA tensor of shape {list(shape)} on the device of points")
+    return t.detach().to(torch.float64).contiguous()
+
+
+def _run_geometry_grad(p, adj, off, bbox, volume, centroid, bounded, grad_volume, grad_centroid):
+    """grad_points f64[N,3]; one synchronisation, to read whether a row was refused."""
+    n, e, dev = p.size(0), adj.numel(), p.device
+    lib = _lib.load()
+    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rf_cell_geometry_grad_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
+    opt = lambda t: None if t is None else _ptr(t)
+    with torch.cuda.device(dev):
+        rc = lib.rf_cell_geometry_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(volume), _ptr(centroid),
+                                       _ptr(bounded), opt(grad_volume), opt(grad_centroid), _ptr(grad), _ptr(status),
+                                       _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc)
+    if n:
+        worst, cell = status.max(0)
+        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
+        if worst:
+            raise RuntimeError(f"cell_geometry_grad: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    return grad
+
+
+def cell_geometry_grad(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
+                       geometry: CellGeometry, grad_volume, grad_centroid) -> torch.Tensor:
+    """f64[N,3]: the gradient with respect to ``points`` of  L = sum_a grad_volume[a] volume[a] + grad_centroid[a] .
+    centroid[a]  over the bounded cells, ``geometry`` being what cell_geometry returned for the same arguments.
+
+    grad p_a = sum over b in a's row of (1 / |p_b - p_a|) int_{F_ab} (phi_a - phi_b)(x) (x - p_a) dA  with
+    phi_a(x) = grad_volume[a] + (grad_centroid[a] / volume[a]) . (x - centroid[a]), and phi_a = 0 for an unbounded cell:
+    whatever arrives for it, NaN and inf included, is ignored.  Either upstream (f64 or f32, [N] and [N,3]) may be None.
+    A gather over each site's own row, bit-reproducible: the exact gradient for a symmetric adjacency such as a
+    Delaunay CSR; where a row omits a site that lists it, the omitted terms are dropped.  Face areas are not
+    differentiated.  Raises RuntimeError naming the cell like cell_geometry."""
+    p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+    n, dev = p.size(0), p.device
+    volume, centroid, bounded = geometry.volume, geometry.centroid, geometry.bounded
+    if (not volume.is_cuda or volume.device != dev or volume.dtype != torch.float64 or volume.shape != (n,)
+            or centroid.device != dev or centroid.dtype != torch.float64 or centroid.shape != (n, 3)
+            or bounded.device != dev or bounded.dtype != torch.bool or bounded.shape != (n,)):
+        raise RuntimeError("geometry must be the CellGeometry cell_geometry returned for these points")
+    return _run_geometry_grad(p, adj, off, bbox, volume.detach().contiguous(), centroid.detach().contiguous(),
+                              bounded.contiguous().view(torch.uint8), _upstream("grad_volume", grad_volume, (n,), dev),
+                              _upstream("grad_centroid", grad_centroid, (n, 3), dev))
+
+
+class _DifferentiableCellGeometry(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, point_adjacency, point_adjacency_offsets):
+        p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+        geo = _run_geometry(p, adj, off, bbox)[0]
+        ctx.save_for_backward(p, adj, off, bbox, geo.volume, geo.centroid, geo.bounded)
+        ctx.points_dtype = points.dtype
+        ctx.mark_non_differentiable(geo.bounded, geo.face_area)
+        return geo.volume, geo.centroid, geo.bounded, geo.face_area
+
+    @staticmethod
+    def backward(ctx, grad_volume, grad_centroid, _grad_bounded, _grad_face_area):
+        p, adj, off, bbox, volume, centroid, bounded = ctx.saved_tensors
+        n, dev = p.size(0), p.device
+        grad = _run_geometry_grad(p, adj, off, bbox, volume, centroid, bounded.view(torch.uint8),
+                                  _upstream("grad_volume", grad_volume, (n,), dev),
+                                  _upstream("grad_centroid", grad_centroid, (n, 3), dev))
+        return grad.to(ctx.points_dtype), None, None
+
+
+def differentiable_cell_geometry(points: torch.Tensor, point_adjacency: torch.Tensor,
+                                 point_adjacency_offsets: torch.Tensor) -> CellGeometry:
+    """cell_geometry, bit for bit, with ``volume`` and ``centroid`` carrying autograd to ``points`` (cell_geometry_grad:
+    summed in double, returned in the dtype of ``points``).  ``bounded`` and ``face_area`` are not differentiable.  Mask
+    the unbounded cells out of a loss (their volume is +inf and their centroid NaN); what flows back for them is
+    ignored."""
+    return CellGeometry(*_DifferentiableCellGeometry.apply(points, point_adjacency, point_adjacency_offsets))
