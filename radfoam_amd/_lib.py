@@ -64,8 +64,8 @@ class LaunchOpts(C.Structure):
     ]
 
 
-# every symbol include/radfoam_hip.h, radfoam_hip_geometry.h, radfoam_hip_geometry_grad.h, radfoam_hip_segments.h and
-# radfoam_hip_composite.h declare:
+# every symbol include/radfoam_hip.h, radfoam_hip_geometry.h, radfoam_hip_geometry_grad.h, radfoam_hip_segments.h,
+# radfoam_hip_composite.h and radfoam_hip_distortion.h declare:
 # name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -130,6 +130,9 @@ SYMBOLS = {
     "rf_composite_rays_per_wave": (_U32, []),
     "rf_composite_entries_forward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _U32, _P, _P]),
     "rf_composite_entries_backward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P]),
+    "rf_distortion_rays_per_wave": (_U32, []),
+    "rf_ray_distortion_forward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "rf_ray_distortion_backward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -10,6 +10,8 @@ device, vectorised torch restatements of the same definitions elsewhere (DESIGN 
 
 ``composite_entries`` is the same compositing for inputs the caller has per ENTRY (a density [S] and any number of
 channels [S, C]), with kernels of its own for float32 tensors on the device (rf_composite.hip).
+``ray_distortion`` is the regulariser that goes with it: Mip-NeRF 360's distortion loss of every ray from the same
+per-entry density, by the same scheme of kernels (rf_distortion.hip).
 """
 from __future__ import annotations
 
@@ -198,6 +200,163 @@ def composite_entries(seg, sigma: torch.Tensor, values: torch.Tensor, backend=No
     if not sigma.is_cuda or sigma.dtype != torch.float32:
         raise RuntimeError("the kernel takes float32 CUDA sigma and values (backend='torch' restates it for anything else)")
     return _CompositeEntries.apply(sigma, values, seg["t_enter"], seg["t_exit"], seg["offsets"])
+
+
+def _check_distortion_inputs(seg, sigma, s_enter, s_exit):
+    if sigma.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("sigma must have float32 or float64 dtype")
+    if (s_enter is None) != (s_exit is None):
+        raise RuntimeError("s_enter and s_exit must both be given or both be omitted")
+    for s in (s_enter, s_exit):
+        if s is not None and (s.dtype != sigma.dtype or s.device != sigma.device):
+            raise RuntimeError("s_enter and s_exit must have the dtype and device of sigma")
+    if sigma.dim() != 1 or (s_enter is not None and (s_enter.dim() != 1 or s_exit.dim() != 1)):
+        raise RuntimeError("expected sigma [S], and s_enter [S] and s_exit [S] where given")
+    offsets = seg["offsets"]
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise RuntimeError("seg['offsets'] must be int64 [R+1]")
+    total = sigma.size(0)
+    if seg["t_enter"].numel() != total or seg["t_exit"].numel() != total or (
+            s_enter is not None and (s_enter.size(0) != total or s_exit.size(0) != total)):
+        raise RuntimeError("sigma, s_enter, s_exit, seg['t_enter'] and seg['t_exit'] must have one element per entry")
+    return offsets.numel() - 1, total
+
+
+def _ray_distortion_torch(offsets, t_enter, t_exit, sigma, s_enter, s_exit):
+    """The definition with the operations of ``_composite_entries_torch``: float64 throughout, the sums over a ray's
+    earlier entries as differences of list-wide cumulative sums, one ``index_add`` over the ray index.  Autograd
+    differentiates it."""
+    dev, dtype = sigma.device, sigma.dtype
+    num_rays, total = offsets.numel() - 1, sigma.size(0)
+    t_enter = t_enter.to(dev).to(torch.float64).reshape(-1)
+    t_exit = t_exit.to(dev).to(torch.float64).reshape(-1)
+    infinite, zero = torch.isinf(t_exit), torch.zeros_like(t_exit)
+    dt = torch.where(infinite, zero, (t_exit - t_enter).clamp_min(0.0))
+    a, b = (t_enter, t_exit) if s_enter is None else (s_enter.to(torch.float64), s_exit.to(torch.float64))
+    mid = torch.where(infinite, zero, (a + b) / 2)                 # selected: no inf * 0, and no gradient either
+    width = torch.where(infinite, zero, (b - a).clamp_min(0.0))
+
+    x = sigma.to(torch.float64) * dt
+    counts = offsets[1:] - offsets[:-1]
+    ray = torch.repeat_interleave(torch.arange(num_rays, device=dev), counts, output_size=total)
+
+    def before(v):                                                 # the sum of v over the ray's earlier entries
+        run0 = torch.cat([v.new_zeros(1), torch.cumsum(v, 0)])     # run0[e] = sum of the entries before e
+        return run0[:-1] - run0[offsets[:-1]][ray]
+
+    weight = torch.exp(-before(x)) * -torch.expm1(-x)
+    per_entry = 2 * weight * (mid * before(weight) - before(weight * mid)) + weight * weight * width / 3
+    return torch.zeros(num_rays, dtype=torch.float64, device=dev).index_add(0, ray, per_entry).to(dtype)
+
+
+class _RayDistortion(torch.autograd.Function):
+    """``ray_distortion`` through the kernels of rf_distortion.hip: float32 CUDA tensors, each gradient only where its
+    input needs one.  Nothing but the inputs is kept for the backward, which sweeps the list twice."""
+
+    @staticmethod
+    def forward(ctx, sigma, t_enter, t_exit, s_enter, s_exit, offsets):
+        from . import _lib
+        from .pipeline import _ptr, _stream_ptr
+
+        dev = sigma.device
+        num_rays, total = offsets.numel() - 1, sigma.size(0)
+        if num_rays >= 2 ** 31:
+            raise RuntimeError("too many rays for the kernel")
+        offsets = offsets.to(dev).contiguous()
+        sigma_c = sigma.detach().contiguous()
+        t_enter_c = t_enter.detach().to(dev).to(torch.float32).reshape(-1).contiguous()
+        t_exit_c = t_exit.detach().to(dev).to(torch.float32).reshape(-1).contiguous()
+        ctx.own_measure = s_enter is not None
+        saved = [sigma_c, t_enter_c, t_exit_c, offsets]
+        if ctx.own_measure:
+            saved += [s_enter.detach().contiguous(), s_exit.detach().contiguous()]
+        ctx.save_for_backward(*saved)
+        ctx.times = tuple((t.dtype, t.device, t.shape) for t in (t_enter, t_exit))
+        if num_rays == 0 or total == 0:
+            return torch.zeros(num_rays, dtype=torch.float32, device=dev)
+        out = torch.empty(num_rays, dtype=torch.float32, device=dev)                     # every element is written
+        measure = saved[4:] if ctx.own_measure else (None, None)
+        with torch.cuda.device(dev):
+            rc = _lib.load().rf_ray_distortion_forward(
+                num_rays, _ptr(offsets), total, _ptr(t_enter_c), _ptr(t_exit_c), _ptr(sigma_c), _ptr(measure[0]),
+                _ptr(measure[1]), _ptr(out), _stream_ptr(dev))
+        _lib.check(rc)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import _lib
+        from .pipeline import _ptr, _stream_ptr
+
+        sigma, t_enter, t_exit, offsets = ctx.saved_tensors[:4]
+        measure = ctx.saved_tensors[4:] if ctx.own_measure else (None, None)
+        dev = sigma.device
+        num_rays, total = offsets.numel() - 1, sigma.size(0)
+        want = ctx.needs_input_grad[:5]
+        # entries outside offsets[0] .. offsets[R] are not written by the kernel: there are none in a sound list
+        grads = [torch.empty_like(sigma) if w else None for w in want]
+        if num_rays > 0 and total > 0 and any(want):
+            grad_out = grad_out.to(torch.float32).contiguous()
+            with torch.cuda.device(dev):
+                rc = _lib.load().rf_ray_distortion_backward(
+                    num_rays, _ptr(offsets), total, _ptr(t_enter), _ptr(t_exit), _ptr(sigma), _ptr(measure[0]),
+                    _ptr(measure[1]), _ptr(grad_out), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]),
+                    _ptr(grads[4]), _stream_ptr(dev))
+            _lib.check(rc)
+        for i, (dtype, device, shape) in zip((1, 2), ctx.times):
+            if grads[i] is not None:
+                grads[i] = grads[i].to(device).to(dtype).reshape(shape)
+        return grads[0], grads[1], grads[2], grads[3], grads[4], None
+
+
+def ray_distortion(seg, sigma: torch.Tensor, s_enter=None, s_exit=None, backend=None) -> torch.Tensor:
+    """[R]: the distortion regulariser of Mip-NeRF 360 for the rays of ``seg`` (the dict ``Pipeline.trace_segments`` or
+    ``trace_differentiable_segments`` returns; ``offsets`` int64 [R+1] and ``t_enter`` / ``t_exit`` [S] are read,
+    ``cells`` is not) with a density ``sigma`` [S] PER ENTRY, float32 or float64.  It is small where a ray's compositing
+    weights sit close together in depth; ``lambda * ray_distortion(...).mean()`` added to a photometric loss removes
+    floaters (examples/distortion_regulariser.py).  Per ray, over its entries i in order (the weights are
+    those of ``composite_entries``):
+
+        dt = 0 where t_exit is infinite, else max(t_exit - t_enter, 0),      x = sigma dt
+        T_i = exp(-(sum of x_k, k < i)),      w_i = T_i (1 - exp(-x_i))
+        a, b = s_enter, s_exit if given, else t_enter, t_exit;      m = (a + b) / 2,      d = max(b - a, 0)
+        out[r] = 2 sum_i w_i (m_i W<_i - M<_i) + (1/3) sum_i w_i^2 d_i,   W<_i = sum_{k<i} w_k,  M<_i = sum_{k<i} w_k m_k
+
+    This ordered form is the definition.  It equals ``sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i`` wherever the
+    midpoints of the entries that carry weight do not decrease along the ray, which holds for a walk.
+
+    ``s_enter`` / ``s_exit`` ([S], dtype and device of ``sigma``; both or neither) measure the distortion in another
+    distance -- normalised, or contracted as s = t / (1 + t) -- while the weights still come from the true t.  THEY MUST
+    BE AN INCREASING FUNCTION OF t: otherwise the midpoints are out of order and the ordered form is no longer the
+    distortion.  An entry with an infinite ``t_exit`` has w = 0, contributes nothing and gets exact zeros in every
+    gradient whatever its ``s_*`` hold; a ray without entries gives 0; a non-finite ``s_*`` at an entry that carries
+    weight gives non-finite numbers.  The result has the dtype of ``sigma``.
+
+    Differentiable in ``sigma``, ``seg["t_enter"]`` and ``seg["t_exit"]`` (which carry the gradient on to the points and
+    the rays when they come from ``trace_differentiable_segments``), and in ``s_enter`` / ``s_exit`` when given: the
+    times then get only the gradient through w, otherwise also the one through m and d.  Both ``max`` follow torch's
+    ``clamp_min``: equality passes the gradient on.
+
+    ``backend``: None, "hip" or "torch", as in ``composite_entries``.  None is "hip" for float32 CUDA ``sigma`` and
+    "torch" for everything else.  "hip" runs the kernels of rf_distortion.hip (one wave owns a run of consecutive rays,
+    segmented scans in double, one rounding to float32, no atomics: the same bits from call to call, gradients
+    included; the times are read as float32).  "torch" restates the definition in float64 with list-wide cumulative
+    sums, differentiated by autograd, on any device; no Python loop over rays.  ``offsets[-1] == S`` is checked on the
+    torch path only, and there only when ``seg["offsets"]`` lives on the CPU.  (The kernels clamp every offset to
+    0 .. S instead.)"""
+    if backend not in (None, "hip", "torch"):
+        raise ValueError("backend must be None, 'hip' or 'torch'")
+    num_rays, total = _check_distortion_inputs(seg, sigma, s_enter, s_exit)
+    if backend is None:
+        backend = "hip" if sigma.is_cuda and sigma.dtype == torch.float32 else "torch"
+    if backend == "torch":
+        if not seg["offsets"].is_cuda and int(seg["offsets"][-1]) != total:
+            raise RuntimeError("seg['offsets'][-1] must be the number of entries")
+        return _ray_distortion_torch(seg["offsets"].to(sigma.device), seg["t_enter"], seg["t_exit"], sigma, s_enter,
+                                     s_exit)
+    if not sigma.is_cuda or sigma.dtype != torch.float32:
+        raise RuntimeError("the kernel takes float32 CUDA sigma (backend='torch' restates it for anything else)")
+    return _RayDistortion.apply(sigma, seg["t_enter"], seg["t_exit"], s_enter, s_exit, seg["offsets"])
 
 
 _NONE = 0xFFFFFFFF
