@@ -7,19 +7,9 @@
 //     T_e = exp(-(sum of x_k over the ray's earlier entries)),      w_e = T_e (1 - exp(-x_e))
 //     out[r][c] = sum_e w_e values[e][c],      out[r][C] = 1 - exp(-(sum_e x_e))
 //
-// ONE WAVE OWNS kCompRays CONSECUTIVE RAYS and sweeps their contiguous range of entries 64 at a time, one lane per
-// entry, from the 64-aligned entry at or below the range's first: every [S] array is read coalesced.  No ray is shared
-// between waves, so nothing is accumulated with atomics and no output is zeroed first: every element is written once and
-// the result is the same bits from call to call.  (rf_segments_rays_grad.hip deals entries to waves evenly instead and
-// finishes a ray with atomics.)  The price is load imbalance when the rays' entry counts differ wildly.
-//
-// The wave keeps its kCompRays + 1 offsets in its first lanes (clamped to 0 .. S and made non-decreasing, so that
-// nothing below can index outside the arrays whatever the list holds).  In a step a lane finds its ray by counting the
-// offsets at or below its entry (they are wave-uniform: scalar reads of those lanes), and its run's first lane from
-// max(offsets[ray], the step's first entry).  The sums over a ray's earlier entries are an INCLUSIVE SEGMENTED SCAN IN
-// DOUBLE over the wave (six steps of distance 1 .. 32, ds_bpermute on the two halves of each double, as in
-// rf_segments_rays_grad.hip); a ray that continues past the step hands its running sums on in wave-uniform registers.
-// The per-channel sums are segmented reductions by the same scan: the last lane of a ray's run in the step holds the
+// The wave scheme -- one wave owns kCompRays consecutive rays and sweeps their entries 64 at a time, segmented scans in
+// double, no atomics, no LDS, no lane returning before the wave's last cross-lane operation -- is rf_ray_sweep.hpp's.
+// Here the per-channel sums are segmented reductions by its scan: the last lane of a ray's run in the step holds the
 // run's sums, adds what the ray carried in, and when the ray ends there rounds ONCE to fp32 and stores the row.
 //
 // Forward: channels go in groups of at most kCompGroup, one launch (one sweep) per group, so that the carried sums stay
@@ -28,16 +18,15 @@
 // ray's total minus an inclusive prefix, so the wave SWEEPS ITS RANGE TWICE: the first sweep leaves the totals of ray
 // r0 + i in lane i, the second forms the gradients.  Nothing is reconstructed from the fp32 output of the forward.
 //
-// NO LANE RETURNS before the last cross-lane operation of its wave (a wave without rays returns whole, before the
-// first).  Lanes outside the wave's range of entries stay, as runs of their own holding zeros; loads and stores are
-// predicated.  No LDS.  Compiled like the tracer (-ffp-contract=off; every fused multiply-add spelled out); exp and
-// expm1 are the double ones.
+// Compiled like the tracer (-ffp-contract=off; every fused multiply-add spelled out); exp and expm1 are the double
+// ones.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 
 #include "../../include/radfoam_hip_composite.h"
 #include "rf_host.hpp"
+#include "rf_ray_sweep.hpp"
 
 #ifndef RF_COMPOSITE_RAYS_PER_WAVE
 #define RF_COMPOSITE_RAYS_PER_WAVE 8
@@ -49,92 +38,9 @@ constexpr int kCompBlock = 256;
 constexpr int kCompWaves = kCompBlock / 64;
 constexpr int kCompRays = RF_COMPOSITE_RAYS_PER_WAVE;      // rays per wave: chosen with scripts/gpu_composite_time.py
 constexpr int kCompGroup = 4;                              // channels per forward sweep
-static_assert(kCompRays >= 1 && kCompRays <= 63, "a wave keeps kCompRays + 1 offsets in its lanes");
-
-// the value lane `src` (0 .. 63) holds, every lane of the wave taking part (rf_segments_rays_grad.hip::segr_from_lane)
-__device__ __forceinline__ uint64_t comp_bits_from_lane(uint64_t bits, int src) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)bits);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)(bits >> 32));
-    return ((uint64_t)hi << 32) | (uint64_t)lo;
-}
-__device__ __forceinline__ double comp_from_lane(double x, int src) {
-    return __builtin_bit_cast(double, comp_bits_from_lane(__builtin_bit_cast(uint64_t, x), src));
-}
-__device__ __forceinline__ int64_t comp_from_lane(int64_t x, int src) {
-    return (int64_t)comp_bits_from_lane((uint64_t)x, src);
-}
-
-// the value of a lane known at compile time, as a scalar
-__device__ __forceinline__ int64_t comp_read_lane(int64_t x, int lane) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)x, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)x >> 32), lane);
-    return (int64_t)(((uint64_t)hi << 32) | (uint64_t)lo);
-}
-__device__ __forceinline__ int64_t comp_uniform(int64_t x) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)x);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | (uint64_t)lo);
-}
-
-// ---- the rays of a wave ----
-struct CompWave {
-    int lane;
-    int64_t r0;        // its first ray
-    int nrays;         // 1 .. kCompRays
-    int64_t off;       // lane i: offsets[r0 + min(i, nrays)], clamped to 0 .. S, non-decreasing over the lanes
-    int64_t lo, hi;    // its entries: off of lane 0 and of lane nrays
-};
-
-// false for a wave without rays: the whole wave leaves, before any cross-lane operation
-__device__ __forceinline__ bool comp_wave(CompWave &w, uint32_t num_rays, int64_t total, const int64_t *offsets) {
-    w.lane = (int)(threadIdx.x & 63u);
-    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    w.r0 = ((int64_t)blockIdx.x * kCompWaves + wave_in_block) * kCompRays;
-    if (w.r0 >= (int64_t)num_rays) return false;
-    const int64_t left = (int64_t)num_rays - w.r0;
-    w.nrays = left < kCompRays ? (int)left : kCompRays;
-    int64_t off = offsets[w.r0 + (w.lane < w.nrays ? w.lane : w.nrays)];
-    off = off < 0 ? 0 : (off > total ? total : off);
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {                     // running maximum: non-decreasing whatever the list holds
-        const int64_t below = comp_from_lane(off, (w.lane - s) & 63);
-        if (w.lane >= s && below > off) off = below;
-    }
-    w.off = off;
-    w.lo = comp_uniform(off);
-    w.hi = comp_read_lane(off, 63);                        // the lanes from nrays on all hold the range's end
-    return true;
-}
-
-// ---- a lane's place in one step of 64 entries ----
-struct CompStep {
-    int64_t k;         // its entry
-    bool valid;        // within the wave's range
-    int ray;           // its ray, counted from r0 (0 where not valid)
-    int begin;         // first lane of its run in this step (itself where not valid)
-    bool cont;         // its ray began before this step: the carried sums belong to it
-    bool ends;         // its ray ends within this step
-    bool last;         // it is the last lane of its run in this step
-};
-
-__device__ __forceinline__ CompStep comp_step(const CompWave &w, int64_t base) {
-    CompStep s;
-    s.k = base + w.lane;
-    s.valid = s.k >= w.lo && s.k < w.hi;
-    int ray = 0;
-#pragma unroll
-    for (int i = 1; i <= kCompRays; ++i) ray += s.k >= comp_read_lane(w.off, i) ? 1 : 0;
-    s.ray = s.valid ? ray : 0;                             // valid: off[ray] <= k < off[ray + 1], ray < nrays
-    const int64_t seg_lo = comp_from_lane(w.off, s.ray);
-    const int64_t seg_hi = comp_from_lane(w.off, s.ray + 1);
-    const int64_t step_end = base + 64;
-    const int end = (int)((seg_hi < step_end ? seg_hi : step_end) - 1 - base);
-    s.begin = s.valid ? (int)((seg_lo > base ? seg_lo : base) - base) : w.lane;
-    s.cont = s.valid && seg_lo < base;
-    s.ends = s.valid && seg_hi <= step_end;
-    s.last = s.valid && w.lane == end;
-    return s;
-}
+using CompSweep = RaySweep<kCompRays, kCompWaves>;
+using CompWave = CompSweep::Wave;
+using CompStep = CompSweep::Step;
 
 // ---- what an entry contributes: zeros where the lane is not valid ----
 struct CompEntry {
@@ -158,28 +64,6 @@ __device__ __forceinline__ CompEntry comp_entry(const CompStep &s, const float *
     return e;
 }
 
-// inclusive segmented scan over the wave: after the step of distance s a lane holds the sum over
-// max(begin, lane - 2s + 1) .. lane.  The source index wraps below lane 0; what comes from there is not added.
-template <int N>
-__device__ __forceinline__ void comp_scan(double (&v)[N], int lane, int begin) {
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const int src = (lane - s) & 63;
-        double u[N];
-#pragma unroll
-        for (int n = 0; n < N; ++n) u[n] = comp_from_lane(v[n], src);
-        if (lane - s >= begin) {
-#pragma unroll
-            for (int n = 0; n < N; ++n) v[n] = v[n] + u[n];
-        }
-    }
-}
-
-// what the ray that runs past the step's last lane hands on: every lane gets it (0 when no ray does)
-__device__ __forceinline__ double comp_carry(const CompStep &s, double sum) {
-    return comp_from_lane(s.last && !s.ends ? sum : 0.0, 63);
-}
-
 struct CompForwardParams {
     uint32_t num_rays, num_channels;
     uint32_t first_channel;      // this launch composites channels first_channel .. first_channel + NCH - 1
@@ -194,12 +78,12 @@ struct CompForwardParams {
 template <int NCH>
 __global__ __launch_bounds__(kCompBlock) void composite_forward_kernel(CompForwardParams p) {
     CompWave w;
-    if (!comp_wave(w, p.num_rays, p.total, p.offsets)) return;
+    if (!w.init(p.num_rays, p.total, p.offsets)) return;
     const size_t pitch = (size_t)p.num_channels + 1;
 
     // rays without entries: lane i answers for ray r0 + i
     {
-        const int64_t next = comp_from_lane(w.off, (w.lane + 1) & 63);
+        const int64_t next = CompSweep::from_lane(w.off, (w.lane + 1) & 63);
         if (w.lane < w.nrays && next == w.off) {
             float *row = p.out + (size_t)(w.r0 + w.lane) * pitch;
 #pragma unroll
@@ -211,8 +95,8 @@ __global__ __launch_bounds__(kCompBlock) void composite_forward_kernel(CompForwa
     double carry_x = 0.0, carry[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) carry[c] = 0.0;
-    for (int64_t base = w.lo & ~(int64_t)63; base < w.hi; base += 64) {
-        const CompStep s = comp_step(w, base);
+    for (int64_t base = w.first_base(); base < w.hi; base += 64) {
+        const CompStep s = CompSweep::step(w, base);
         const CompEntry e = comp_entry(s, p.t_enter, p.t_exit, p.sigma);
         double v[NCH];
 #pragma unroll
@@ -224,12 +108,12 @@ __global__ __launch_bounds__(kCompBlock) void composite_forward_kernel(CompForwa
         }
 
         double sx[1] = {e.x};
-        comp_scan(sx, w.lane, s.begin);
+        CompSweep::scan(sx, w.lane, s.begin);
         const double sum_x = s.cont ? sx[0] + carry_x : sx[0];          // the ray's x up to and including this entry
         const double weight = ::exp(-(sum_x - e.x)) * -::expm1(-e.x);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) v[c] = weight * v[c];
-        comp_scan(v, w.lane, s.begin);
+        CompSweep::scan(v, w.lane, s.begin);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) v[c] = s.cont ? v[c] + carry[c] : v[c];
 
@@ -239,9 +123,9 @@ __global__ __launch_bounds__(kCompBlock) void composite_forward_kernel(CompForwa
             for (int c = 0; c < NCH; ++c) row[p.first_channel + c] = (float)v[c];
             if (p.write_alpha) row[p.num_channels] = (float)-::expm1(-sum_x);
         }
-        carry_x = comp_carry(s, sum_x);
+        carry_x = CompSweep::carry(s, sum_x);
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) carry[c] = comp_carry(s, v[c]);
+        for (int c = 0; c < NCH; ++c) carry[c] = CompSweep::carry(s, v[c]);
     }
 }
 
@@ -256,7 +140,7 @@ struct CompBackwardParams {
 
 __global__ __launch_bounds__(kCompBlock) void composite_backward_kernel(CompBackwardParams p) {
     CompWave w;
-    if (!comp_wave(w, p.num_rays, p.total, p.offsets)) return;
+    if (!w.init(p.num_rays, p.total, p.offsets)) return;
     const uint32_t C = p.num_channels;
     const size_t pitch = (size_t)C + 1;
     const bool need_x = p.grad_sigma != nullptr || p.grad_t_enter != nullptr || p.grad_t_exit != nullptr;
@@ -264,12 +148,12 @@ __global__ __launch_bounds__(kCompBlock) void composite_backward_kernel(CompBack
     // ---- first sweep: lane i gets sum x and sum w q of ray r0 + i, from the lane of the ray's last entry ----
     double ray_x = 0.0, ray_wq = 0.0;
     if (need_x) {
-        const int64_t next = comp_from_lane(w.off, (w.lane + 1) & 63);
+        const int64_t next = CompSweep::from_lane(w.off, (w.lane + 1) & 63);
         const bool mine = w.lane < w.nrays && next > w.off;
         const int64_t my_last = next - 1;
         double carry_x = 0.0, carry_wq = 0.0;
-        for (int64_t base = w.lo & ~(int64_t)63; base < w.hi; base += 64) {
-            const CompStep s = comp_step(w, base);
+        for (int64_t base = w.first_base(); base < w.hi; base += 64) {
+            const CompStep s = CompSweep::step(w, base);
             const CompEntry e = comp_entry(s, p.t_enter, p.t_exit, p.sigma);
             double q = 0.0;
             if (s.valid) {
@@ -278,38 +162,38 @@ __global__ __launch_bounds__(kCompBlock) void composite_backward_kernel(CompBack
                 for (uint32_t c = 0; c < C; ++c) q = __builtin_fma((double)g[c], (double)row[c], q);
             }
             double sx[1] = {e.x};
-            comp_scan(sx, w.lane, s.begin);
+            CompSweep::scan(sx, w.lane, s.begin);
             const double sum_x = s.cont ? sx[0] + carry_x : sx[0];
             const double weight = ::exp(-(sum_x - e.x)) * -::expm1(-e.x);
             double swq[1] = {weight * q};
-            comp_scan(swq, w.lane, s.begin);
+            CompSweep::scan(swq, w.lane, s.begin);
             const double sum_wq = s.cont ? swq[0] + carry_wq : swq[0];
 
             const bool here = mine && my_last >= base && my_last < base + 64;
             const int src = here ? (int)(my_last - base) : w.lane;
-            const double end_x = comp_from_lane(sum_x, src), end_wq = comp_from_lane(sum_wq, src);
+            const double end_x = CompSweep::from_lane(sum_x, src), end_wq = CompSweep::from_lane(sum_wq, src);
             if (here) {
                 ray_x = end_x;
                 ray_wq = end_wq;
             }
-            carry_x = comp_carry(s, sum_x);
-            carry_wq = comp_carry(s, sum_wq);
+            carry_x = CompSweep::carry(s, sum_x);
+            carry_wq = CompSweep::carry(s, sum_wq);
         }
     }
     const double ray_keep = ::exp(-ray_x);                       // what the whole ray lets through
 
     // ---- second sweep: the gradients ----
     double carry_x = 0.0, carry_wq = 0.0;
-    for (int64_t base = w.lo & ~(int64_t)63; base < w.hi; base += 64) {
-        const CompStep s = comp_step(w, base);
+    for (int64_t base = w.first_base(); base < w.hi; base += 64) {
+        const CompStep s = CompSweep::step(w, base);
         const CompEntry e = comp_entry(s, p.t_enter, p.t_exit, p.sigma);
         double sx[1] = {e.x};
-        comp_scan(sx, w.lane, s.begin);
+        CompSweep::scan(sx, w.lane, s.begin);
         const double sum_x = s.cont ? sx[0] + carry_x : sx[0];
         const double through = ::exp(-(sum_x - e.x));            // T_e
         const double alpha = -::expm1(-e.x);
         const double weight = through * alpha;
-        carry_x = comp_carry(s, sum_x);
+        carry_x = CompSweep::carry(s, sum_x);
 
         double q = 0.0;
         if (s.valid) {
@@ -325,10 +209,11 @@ __global__ __launch_bounds__(kCompBlock) void composite_backward_kernel(CompBack
         if (!need_x) continue;                                           // wave-uniform
 
         double swq[1] = {weight * q};
-        comp_scan(swq, w.lane, s.begin);
+        CompSweep::scan(swq, w.lane, s.begin);
         const double sum_wq = s.cont ? swq[0] + carry_wq : swq[0];
-        carry_wq = comp_carry(s, sum_wq);
-        const double keep = comp_from_lane(ray_keep, s.ray), total_wq = comp_from_lane(ray_wq, s.ray);
+        carry_wq = CompSweep::carry(s, sum_wq);
+        const double keep = CompSweep::from_lane(ray_keep, s.ray);
+        const double total_wq = CompSweep::from_lane(ray_wq, s.ray);
         if (s.valid) {
             const double g_alpha = (double)p.grad_out[(size_t)(w.r0 + s.ray) * pitch + C];
             // T_e exp(-x_e) q_e - (the ray's later w q) + G[r][C] exp(-sum x); exp(-x_e) = 1 - alpha_e
@@ -348,15 +233,10 @@ using namespace rf;
 
 namespace {
 
-int64_t comp_blocks(uint32_t num_rays) {
-    const int64_t waves = ((int64_t)num_rays + kCompRays - 1) / kCompRays;
-    return (waves + kCompWaves - 1) / kCompWaves;
-}
-
 template <int NCH>
 void comp_launch_forward(const CompForwardParams &p, hipStream_t stream) {
-    hipLaunchKernelGGL(composite_forward_kernel<NCH>, dim3((uint32_t)comp_blocks(p.num_rays)), dim3(kCompBlock), 0,
-                       stream, p);
+    hipLaunchKernelGGL(composite_forward_kernel<NCH>, dim3((uint32_t)CompSweep::blocks(p.num_rays)), dim3(kCompBlock),
+                       0, stream, p);
 }
 
 }  // namespace
@@ -433,7 +313,7 @@ int rf_composite_entries_backward(uint32_t num_rays, const int64_t *offsets, int
     p.grad_values = grad_values;
     p.grad_t_enter = grad_t_enter;
     p.grad_t_exit = grad_t_exit;
-    hipLaunchKernelGGL(composite_backward_kernel, dim3((uint32_t)comp_blocks(num_rays)), dim3(kCompBlock), 0,
+    hipLaunchKernelGGL(composite_backward_kernel, dim3((uint32_t)CompSweep::blocks(num_rays)), dim3(kCompBlock), 0,
                        static_cast<hipStream_t>(stream), p);
     return check_launch(what);
 }

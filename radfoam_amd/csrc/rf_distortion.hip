@@ -8,15 +8,8 @@
 //     m_i = (a_i + b_i) / 2,   d_i = max(b_i - a_i, 0);   both 0, selected, where t_exit[i] is infinite
 //     out[r] = 2 sum_i w_i (m_i W<_i - M<_i) + (1/3) sum_i w_i^2 d_i,      W<_i = sum_{k<i} w_k, M<_i = sum_{k<i} w_k m_k
 //
-// THE SCHEME IS rf_composite.hip's, restated here because that file and rf_wave.hpp stay byte for byte: ONE WAVE OWNS
-// kDistRays CONSECUTIVE RAYS and sweeps their contiguous range of entries 64 at a time, one lane per entry, from the
-// 64-aligned entry at or below the range's first, so every [S] array is read coalesced.  No ray is shared between waves:
-// nothing is accumulated with atomics, no output is zeroed first, every element is written once and the result is the
-// same bits from call to call.  The wave keeps its kDistRays + 1 offsets in its first lanes (clamped to 0 .. S and made
-// non-decreasing, so that nothing below can index outside the arrays whatever the list holds); a lane finds its ray by
-// counting the offsets at or below its entry.  The sums over a ray's earlier entries are INCLUSIVE SEGMENTED SCANS IN
-// DOUBLE over the wave (six steps of distance 1 .. 32, ds_bpermute on the two halves of each double); a ray that
-// continues past the step hands its running sums on in wave-uniform registers.
+// The wave scheme -- one wave owns kDistRays consecutive rays and sweeps their entries 64 at a time, segmented scans in
+// double, no atomics, no LDS, no lane returning before the wave's last cross-lane operation -- is rf_ray_sweep.hpp's.
 //
 // A sweep scans three times per step: x (for T and w), then w and w m together (W< and M< are the inclusive sums less
 // the lane's own term), then the entry's share of out[r].  The sums over a ray's LATER entries, which only the
@@ -26,15 +19,14 @@
 // inclusive prefix: no third sweep.  The forward stores from those lanes: lane i rounds ONCE to fp32 and writes out[r0 + i]
 // (0 for a ray without entries).  Nothing is reconstructed from the fp32 output of the forward.
 //
-// NO LANE RETURNS before the last cross-lane operation of its wave (a wave without rays returns whole, before the
-// first).  Lanes outside the wave's range of entries stay, as runs of their own holding zeros; loads and stores are
-// predicated.  No LDS.  Compiled like the tracer (-ffp-contract=off); exp and expm1 are the double ones.
+// Compiled like the tracer (-ffp-contract=off); exp and expm1 are the double ones.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 
 #include "../../include/radfoam_hip_distortion.h"
 #include "rf_host.hpp"
+#include "rf_ray_sweep.hpp"
 
 #ifndef RF_DISTORTION_RAYS_PER_WAVE
 #define RF_DISTORTION_RAYS_PER_WAVE 8
@@ -45,92 +37,9 @@ namespace rf {
 constexpr int kDistBlock = 256;
 constexpr int kDistWaves = kDistBlock / 64;
 constexpr int kDistRays = RF_DISTORTION_RAYS_PER_WAVE;     // rays per wave: 8 and 16 measured equal, 2, 4, 32 slower
-static_assert(kDistRays >= 1 && kDistRays <= 63, "a wave keeps kDistRays + 1 offsets in its lanes");
-
-// the value lane `src` (0 .. 63) holds, every lane of the wave taking part (rf_composite.hip::comp_from_lane)
-__device__ __forceinline__ uint64_t dist_bits_from_lane(uint64_t bits, int src) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)bits);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)(bits >> 32));
-    return ((uint64_t)hi << 32) | (uint64_t)lo;
-}
-__device__ __forceinline__ double dist_from_lane(double x, int src) {
-    return __builtin_bit_cast(double, dist_bits_from_lane(__builtin_bit_cast(uint64_t, x), src));
-}
-__device__ __forceinline__ int64_t dist_from_lane(int64_t x, int src) {
-    return (int64_t)dist_bits_from_lane((uint64_t)x, src);
-}
-
-// the value of a lane known at compile time, as a scalar
-__device__ __forceinline__ int64_t dist_read_lane(int64_t x, int lane) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)x, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)x >> 32), lane);
-    return (int64_t)(((uint64_t)hi << 32) | (uint64_t)lo);
-}
-__device__ __forceinline__ int64_t dist_uniform(int64_t x) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)x);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | (uint64_t)lo);
-}
-
-// ---- the rays of a wave ----
-struct DistWave {
-    int lane;
-    int64_t r0;        // its first ray
-    int nrays;         // 1 .. kDistRays
-    int64_t off;       // lane i: offsets[r0 + min(i, nrays)], clamped to 0 .. S, non-decreasing over the lanes
-    int64_t lo, hi;    // its entries: off of lane 0 and of lane nrays
-};
-
-// false for a wave without rays: the whole wave leaves, before any cross-lane operation
-__device__ __forceinline__ bool dist_wave(DistWave &w, uint32_t num_rays, int64_t total, const int64_t *offsets) {
-    w.lane = (int)(threadIdx.x & 63u);
-    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    w.r0 = ((int64_t)blockIdx.x * kDistWaves + wave_in_block) * kDistRays;
-    if (w.r0 >= (int64_t)num_rays) return false;
-    const int64_t left = (int64_t)num_rays - w.r0;
-    w.nrays = left < kDistRays ? (int)left : kDistRays;
-    int64_t off = offsets[w.r0 + (w.lane < w.nrays ? w.lane : w.nrays)];
-    off = off < 0 ? 0 : (off > total ? total : off);
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {                     // running maximum: non-decreasing whatever the list holds
-        const int64_t below = dist_from_lane(off, (w.lane - s) & 63);
-        if (w.lane >= s && below > off) off = below;
-    }
-    w.off = off;
-    w.lo = dist_uniform(off);
-    w.hi = dist_read_lane(off, 63);                        // the lanes from nrays on all hold the range's end
-    return true;
-}
-
-// ---- a lane's place in one step of 64 entries ----
-struct DistStep {
-    int64_t k;         // its entry
-    bool valid;        // within the wave's range
-    int ray;           // its ray, counted from r0 (0 where not valid)
-    int begin;         // first lane of its run in this step (itself where not valid)
-    bool cont;         // its ray began before this step: the carried sums belong to it
-    bool ends;         // its ray ends within this step
-    bool last;         // it is the last lane of its run in this step
-};
-
-__device__ __forceinline__ DistStep dist_step(const DistWave &w, int64_t base) {
-    DistStep s;
-    s.k = base + w.lane;
-    s.valid = s.k >= w.lo && s.k < w.hi;
-    int ray = 0;
-#pragma unroll
-    for (int i = 1; i <= kDistRays; ++i) ray += s.k >= dist_read_lane(w.off, i) ? 1 : 0;
-    s.ray = s.valid ? ray : 0;                             // valid: off[ray] <= k < off[ray + 1], ray < nrays
-    const int64_t seg_lo = dist_from_lane(w.off, s.ray);
-    const int64_t seg_hi = dist_from_lane(w.off, s.ray + 1);
-    const int64_t step_end = base + 64;
-    const int end = (int)((seg_hi < step_end ? seg_hi : step_end) - 1 - base);
-    s.begin = s.valid ? (int)((seg_lo > base ? seg_lo : base) - base) : w.lane;
-    s.cont = s.valid && seg_lo < base;
-    s.ends = s.valid && seg_hi <= step_end;
-    s.last = s.valid && w.lane == end;
-    return s;
-}
+using DistSweep = RaySweep<kDistRays, kDistWaves>;
+using DistWave = DistSweep::Wave;
+using DistStep = DistSweep::Step;
 
 // ---- what an entry brings: zeros where the lane is not valid ----
 struct DistEntry {
@@ -161,28 +70,6 @@ __device__ __forceinline__ DistEntry dist_entry(const DistStep &s, const float *
     return e;
 }
 
-// inclusive segmented scan over the wave: after the step of distance s a lane holds the sum over
-// max(begin, lane - 2s + 1) .. lane.  The source index wraps below lane 0; what comes from there is not added.
-template <int N>
-__device__ __forceinline__ void dist_scan(double (&v)[N], int lane, int begin) {
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const int src = (lane - s) & 63;
-        double u[N];
-#pragma unroll
-        for (int n = 0; n < N; ++n) u[n] = dist_from_lane(v[n], src);
-        if (lane - s >= begin) {
-#pragma unroll
-            for (int n = 0; n < N; ++n) v[n] = v[n] + u[n];
-        }
-    }
-}
-
-// what the ray that runs past the step's last lane hands on: every lane gets it (0 when no ray does)
-__device__ __forceinline__ double dist_carry(const DistStep &s, double sum) {
-    return dist_from_lane(s.last && !s.ends ? sum : 0.0, 63);
-}
-
 // ---- the weights of a step and their running sums ----
 struct DistCarry {
     double x, w, wm;   // of the ray that runs past the step before: sum x, sum w, sum w m so far
@@ -200,21 +87,21 @@ __device__ __forceinline__ DistWeights dist_weights(const DistWave &wv, const Di
                                                     DistCarry &carry) {
     DistWeights o;
     double sx[1] = {e.x};
-    dist_scan(sx, wv.lane, s.begin);
+    DistSweep::scan(sx, wv.lane, s.begin);
     const double sum_x = s.cont ? sx[0] + carry.x : sx[0];
     o.through = ::exp(-(sum_x - e.x));
     o.alpha = -::expm1(-e.x);
     o.w = o.through * o.alpha;
     const double wm = o.w * e.m;
     double v[2] = {o.w, wm};
-    dist_scan(v, wv.lane, s.begin);
+    DistSweep::scan(v, wv.lane, s.begin);
     o.upto_w = s.cont ? v[0] + carry.w : v[0];
     o.upto_wm = s.cont ? v[1] + carry.wm : v[1];
     o.before_w = o.upto_w - o.w;
     o.before_wm = o.upto_wm - wm;
-    carry.x = dist_carry(s, sum_x);
-    carry.w = dist_carry(s, o.upto_w);
-    carry.wm = dist_carry(s, o.upto_wm);
+    carry.x = DistSweep::carry(s, sum_x);
+    carry.w = DistSweep::carry(s, o.upto_w);
+    carry.wm = DistSweep::carry(s, o.upto_wm);
     return o;
 }
 
@@ -234,25 +121,25 @@ struct DistParams {
 __device__ __forceinline__ void dist_totals(const DistWave &w, const DistParams &p, double &ray_w, double &ray_wm,
                                             double &ray_out) {
     ray_w = ray_wm = ray_out = 0.0;
-    const int64_t next = dist_from_lane(w.off, (w.lane + 1) & 63);
+    const int64_t next = DistSweep::from_lane(w.off, (w.lane + 1) & 63);
     const bool mine = w.lane < w.nrays && next > w.off;
     const int64_t my_last = next - 1;
     DistCarry carry{0.0, 0.0, 0.0};
     double carry_out = 0.0;
-    for (int64_t base = w.lo & ~(int64_t)63; base < w.hi; base += 64) {
-        const DistStep s = dist_step(w, base);
+    for (int64_t base = w.first_base(); base < w.hi; base += 64) {
+        const DistStep s = DistSweep::step(w, base);
         const DistEntry e = dist_entry(s, p.t_enter, p.t_exit, p.sigma, p.s_enter, p.s_exit);
         const DistWeights q = dist_weights(w, s, e, carry);
         // the entry's share: 2 w (m W< - M<) + w^2 d / 3
         double share[1] = {2.0 * q.w * (e.m * q.before_w - q.before_wm) + q.w * q.w * e.d / 3.0};
-        dist_scan(share, w.lane, s.begin);
+        DistSweep::scan(share, w.lane, s.begin);
         const double sum_out = s.cont ? share[0] + carry_out : share[0];
-        carry_out = dist_carry(s, sum_out);
+        carry_out = DistSweep::carry(s, sum_out);
 
         const bool here = mine && my_last >= base && my_last < base + 64;
         const int src = here ? (int)(my_last - base) : w.lane;
-        const double end_w = dist_from_lane(q.upto_w, src), end_wm = dist_from_lane(q.upto_wm, src);
-        const double end_out = dist_from_lane(sum_out, src);
+        const double end_w = DistSweep::from_lane(q.upto_w, src), end_wm = DistSweep::from_lane(q.upto_wm, src);
+        const double end_out = DistSweep::from_lane(sum_out, src);
         if (here) {
             ray_w = end_w;
             ray_wm = end_wm;
@@ -263,7 +150,7 @@ __device__ __forceinline__ void dist_totals(const DistWave &w, const DistParams 
 
 __global__ __launch_bounds__(kDistBlock) void ray_distortion_forward_kernel(DistParams p) {
     DistWave w;
-    if (!dist_wave(w, p.num_rays, p.total, p.offsets)) return;
+    if (!w.init(p.num_rays, p.total, p.offsets)) return;
     double ray_w, ray_wm, ray_out;
     dist_totals(w, p, ray_w, ray_wm, ray_out);
     if (w.lane < w.nrays) p.out[w.r0 + w.lane] = (float)ray_out;         // the ray's sum is complete: round once
@@ -271,7 +158,7 @@ __global__ __launch_bounds__(kDistBlock) void ray_distortion_forward_kernel(Dist
 
 __global__ __launch_bounds__(kDistBlock) void ray_distortion_backward_kernel(DistParams p) {
     DistWave w;
-    if (!dist_wave(w, p.num_rays, p.total, p.offsets)) return;
+    if (!w.init(p.num_rays, p.total, p.offsets)) return;
     const bool need_x = p.grad_sigma != nullptr || p.grad_t_enter != nullptr || p.grad_t_exit != nullptr;
     const bool own_measure = p.s_enter != nullptr;                       // the times get the part through w alone
 
@@ -282,12 +169,12 @@ __global__ __launch_bounds__(kDistBlock) void ray_distortion_backward_kernel(Dis
     // ---- second sweep: the gradients ----
     DistCarry carry{0.0, 0.0, 0.0};
     double carry_wg = 0.0;
-    for (int64_t base = w.lo & ~(int64_t)63; base < w.hi; base += 64) {
-        const DistStep s = dist_step(w, base);
+    for (int64_t base = w.first_base(); base < w.hi; base += 64) {
+        const DistStep s = DistSweep::step(w, base);
         const DistEntry e = dist_entry(s, p.t_enter, p.t_exit, p.sigma, p.s_enter, p.s_exit);
         const DistWeights q = dist_weights(w, s, e, carry);
-        const double total_w = dist_from_lane(ray_w, s.ray), total_wm = dist_from_lane(ray_wm, s.ray);
-        const double total_out = dist_from_lane(ray_out, s.ray);
+        const double total_w = DistSweep::from_lane(ray_w, s.ray), total_wm = DistSweep::from_lane(ray_wm, s.ray);
+        const double total_out = DistSweep::from_lane(ray_out, s.ray);
         const double after_w = total_w - q.upto_w, after_wm = total_wm - q.upto_wm;      // W>_i, M>_i
         const double g_ray = s.valid ? (double)p.grad_out[w.r0 + s.ray] : 0.0;
 
@@ -306,9 +193,9 @@ __global__ __launch_bounds__(kDistBlock) void ray_distortion_backward_kernel(Dis
         const double g_w = 2.0 * (e.m * q.before_w - q.before_wm) + 2.0 * (after_wm - e.m * after_w)
                            + 2.0 * q.w * e.d / 3.0;
         double swg[1] = {q.w * g_w};
-        dist_scan(swg, w.lane, s.begin);
+        DistSweep::scan(swg, w.lane, s.begin);
         const double sum_wg = s.cont ? swg[0] + carry_wg : swg[0];
-        carry_wg = dist_carry(s, sum_wg);
+        carry_wg = DistSweep::carry(s, sum_wg);
         if (s.valid) {
             // T_i exp(-x_i) g_i - (the ray's later w g); exp(-x_i) = 1 - alpha_i
             const double dx = g_ray * (q.through * (1.0 - q.alpha) * g_w - (2.0 * total_out - sum_wg));
@@ -324,15 +211,6 @@ __global__ __launch_bounds__(kDistBlock) void ray_distortion_backward_kernel(Dis
 }  // namespace rf
 
 using namespace rf;
-
-namespace {
-
-int64_t dist_blocks(uint32_t num_rays) {
-    const int64_t waves = ((int64_t)num_rays + kDistRays - 1) / kDistRays;
-    return (waves + kDistWaves - 1) / kDistWaves;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -364,7 +242,8 @@ int rf_ray_distortion_forward(uint32_t num_rays, const int64_t *offsets, int64_t
     p.s_enter = s_enter;
     p.s_exit = s_exit;
     p.out = out;
-    hipLaunchKernelGGL(ray_distortion_forward_kernel, dim3((uint32_t)dist_blocks(num_rays)), dim3(kDistBlock), 0, s, p);
+    hipLaunchKernelGGL(ray_distortion_forward_kernel, dim3((uint32_t)DistSweep::blocks(num_rays)), dim3(kDistBlock), 0,
+                       s, p);
     return check_launch(what);
 }
 
@@ -398,7 +277,7 @@ int rf_ray_distortion_backward(uint32_t num_rays, const int64_t *offsets, int64_
     p.grad_t_exit = grad_t_exit;
     p.grad_s_enter = grad_s_enter;
     p.grad_s_exit = grad_s_exit;
-    hipLaunchKernelGGL(ray_distortion_backward_kernel, dim3((uint32_t)dist_blocks(num_rays)), dim3(kDistBlock), 0,
+    hipLaunchKernelGGL(ray_distortion_backward_kernel, dim3((uint32_t)DistSweep::blocks(num_rays)), dim3(kDistBlock), 0,
                        static_cast<hipStream_t>(stream), p);
     return check_launch(what);
 }

@@ -25,6 +25,7 @@
 #include "../../include/radfoam_hip_segments.h"
 #include "rf_host.hpp"
 #include "rf_math.hpp"
+#include "rf_segments_face.hpp"
 
 namespace rf {
 
@@ -47,10 +48,6 @@ struct SegGradParams {
 // gradient accumulation: hardware fp32 atomic add without return, as rf_kernels.hip issues it
 __device__ __forceinline__ void seg_grad_add(float *dst, float v) { unsafeAtomicAdd(dst, v); }
 
-__device__ __forceinline__ double seg_dot3(double ax, double ay, double az, double bx, double by, double bz) {
-    return __builtin_fma(ax, bx, __builtin_fma(ay, by, az * bz));
-}
-
 // rf_math.hpp::bisector_grad -- d(t)/d(p) of the ray's crossing of the bisector of (p, q), the reference's
 // cell_intersection_grad on the fp32 points -- with the fp32 values widened and every operation in double.  The
 // formula divides by dp^2, dp = (q - p) . d, and on a face the ray nearly grazes dp is what is left of a cancellation:
@@ -71,20 +68,6 @@ __device__ __forceinline__ void seg_bisector_grad(double px, double py, double p
     gx = __builtin_fma(num, dx, dp * (ox - px)) / den;
     gy = __builtin_fma(num, dy, dp * (oy - py)) / den;
     gz = __builtin_fma(num, dz, dp * (oz - pz)) / den;
-}
-
-// G of face j (see above); hi is the end of the ray's range.  0 for a face without a far side.
-__device__ __forceinline__ float seg_face_total(const SegGradParams &p, int64_t j, int64_t hi) {
-    const float t1 = p.t_exit[j];
-    if (t1 == __builtin_inff()) return 0.0f;
-    float G = p.g_exit[j];
-    if (t1 > p.t_enter[j]) {
-        for (int64_t m = j + 1; m < hi; ++m) {
-            G = G + p.g_enter[m];
-            if (p.t_exit[m] > p.t_enter[m]) break;
-        }
-    }
-    return G;
 }
 
 __global__ __launch_bounds__(kSegGradBlock) void segments_points_grad_kernel(SegGradParams p) {

@@ -7,16 +7,17 @@
 //     dt/dO = -n / dp
 //     dt/dD = -num / (dp^2 |D|) (n - dp d)          (dt/dd = -num n / dp^2 through (I - d d^T) / |D|: nothing along D)
 //     ray_grad[r][0:3] = sum over the ray's entries of G_j dt/dO,   ray_grad[r][3:6] = sum of G_j dt/dD
-// with G_j the holder-aware total of section 4.9 (seg_face_total below is rf_segments_grad.hip's).  Faces with
+// with G_j the holder-aware total of section 4.9 (rf_segments_face.hpp::seg_face_total).  Faces with
 // G_j == 0 exactly, or without a next cell, add nothing; dp = 0 gives non-finite values in that ray's row.
 //
 // ONE LANE PER ENTRY, 256 per block, every [S] array read coalesced.  A lane forms its six contributions in double on
 // the widened fp32 inputs (dp is what a cancellation leaves and the grazing faces carry the result: section 4.9).  The
 // entries of a ray are consecutive, so the six sums of a ray are a SEGMENTED REDUCTION: the wave runs an inclusive
-// segmented scan in double over its 64 lanes (six steps, distance 1 .. 32, ds_bpermute on the two halves of each
-// double), and the last lane of every run rounds to fp32 once and issues the six atomics: at most one update of a ray's
-// row per (wave, ray) pair, exactly one for a ray that fits in a wave.  A lane knows where its run begins in the wave
-// from data it has anyway: max(offsets[ray], the wave's first entry) - the wave's first entry.
+// segmented scan in double over its 64 lanes (six steps, distance 1 .. 32, rf_ray_sweep.hpp's exchange of a double:
+// ds_bpermute on its two halves), and the last lane of every run rounds to fp32 once and issues the six atomics: at
+// most one update of a ray's row per (wave, ray) pair, exactly one for a ray that fits in a wave.  A lane knows where
+// its run begins in the wave from data it has anyway: max(offsets[ray], the wave's first entry) - the wave's first
+// entry.
 //
 // NO LANE RETURNS before the last cross-lane operation.  Lanes past the end of the list, lanes whose entry_ray is out
 // of range or does not match the offsets, faces without a next cell and faces with G == 0 all stay and carry zeros;
@@ -32,6 +33,8 @@
 #include "../../include/radfoam_hip_segments.h"
 #include "rf_host.hpp"
 #include "rf_math.hpp"
+#include "rf_ray_sweep.hpp"
+#include "rf_segments_face.hpp"
 #include "rf_wave.hpp"
 
 namespace rf {
@@ -51,33 +54,6 @@ struct SegRaysParams {
     const float *g_enter, *g_exit;
     float *ray_grad;             // [R][6], accumulated into
 };
-
-__device__ __forceinline__ double segr_dot3(double ax, double ay, double az, double bx, double by, double bz) {
-    return __builtin_fma(ax, bx, __builtin_fma(ay, by, az * bz));
-}
-
-// G of face j (rf_segments_grad.hip::seg_face_total); hi is the end of the ray's range.  0 for a face without a far
-// side.
-__device__ __forceinline__ float segr_face_total(const SegRaysParams &p, int64_t j, int64_t hi) {
-    const float t1 = p.t_exit[j];
-    if (t1 == __builtin_inff()) return 0.0f;
-    float G = p.g_exit[j];
-    if (t1 > p.t_enter[j]) {
-        for (int64_t m = j + 1; m < hi; ++m) {
-            G = G + p.g_enter[m];
-            if (p.t_exit[m] > p.t_enter[m]) break;
-        }
-    }
-    return G;
-}
-
-// the double of lane `src` (0 .. 63), every lane of the wave taking part
-__device__ __forceinline__ double segr_from_lane(double x, int src) {
-    const uint64_t bits = __builtin_bit_cast(uint64_t, x);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)bits);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)(bits >> 32));
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | (uint64_t)lo);
-}
 
 __global__ __launch_bounds__(kSegRaysBlock) void segments_rays_grad_kernel(SegRaysParams p) {
     const int lane = (int)(threadIdx.x & 63u);
@@ -108,12 +84,12 @@ __global__ __launch_bounds__(kSegRaysBlock) void segments_rays_grad_kernel(SegRa
     if (sound) {
         const uint32_t a = p.cells[k];
         const uint32_t b = k + 1 == hi ? p.exit_cells[ray] : p.cells[k + 1];
-        const float Gf = (a < p.num_points && b < p.num_points) ? segr_face_total(p, k, hi) : 0.0f;
+        const float Gf = (a < p.num_points && b < p.num_points) ? seg_face_total(p, k, hi) : 0.0f;
         if (Gf != 0.0f) {
             const float *rp = p.rays + (size_t)ray * 6;
             const double Ox = rp[0], Oy = rp[1], Oz = rp[2];
             const double Dx = rp[3], Dy = rp[4], Dz = rp[5];
-            const double nrm = __builtin_sqrt(segr_dot3(Dx, Dy, Dz, Dx, Dy, Dz));
+            const double nrm = __builtin_sqrt(seg_dot3(Dx, Dy, Dz, Dx, Dy, Dz));
             const double dx = Dx / nrm, dy = Dy / nrm, dz = Dz / nrm;
             const float *pa = p.points + (size_t)a * 3;
             const float *pb = p.points + (size_t)b * 3;
@@ -121,8 +97,8 @@ __global__ __launch_bounds__(kSegRaysBlock) void segments_rays_grad_kernel(SegRa
             const double bx = pb[0], by = pb[1], bz = pb[2];
             const double nx = bx - ax, ny = by - ay, nz = bz - az;
             const double mx = (ax + bx) / 2.0 - Ox, my = (ay + by) / 2.0 - Oy, mz = (az + bz) / 2.0 - Oz;
-            const double num = segr_dot3(mx, my, mz, nx, ny, nz);
-            const double dp = segr_dot3(nx, ny, nz, dx, dy, dz);
+            const double num = seg_dot3(mx, my, mz, nx, ny, nz);
+            const double dp = seg_dot3(nx, ny, nz, dx, dy, dz);
             const double G = Gf;
             const double wo = -G / dp;                                   // G dt/dO = wo n
             const double wd = -(G * num) / ((dp * dp) * nrm);            // G dt/dD = wd (n - dp d)
@@ -149,8 +125,9 @@ __global__ __launch_bounds__(kSegRaysBlock) void segments_rays_grad_kernel(SegRa
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1) {
         const int src = (lane - s) & 63;
-        const double u0 = segr_from_lane(v0, src), u1 = segr_from_lane(v1, src), u2 = segr_from_lane(v2, src);
-        const double u3 = segr_from_lane(v3, src), u4 = segr_from_lane(v4, src), u5 = segr_from_lane(v5, src);
+        const double u0 = WaveLanes::from_lane(v0, src), u1 = WaveLanes::from_lane(v1, src);
+        const double u2 = WaveLanes::from_lane(v2, src), u3 = WaveLanes::from_lane(v3, src);
+        const double u4 = WaveLanes::from_lane(v4, src), u5 = WaveLanes::from_lane(v5, src);
         if (lane - s >= begin) {
             v0 = v0 + u0;
             v1 = v1 + u1;

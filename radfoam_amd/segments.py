@@ -18,6 +18,50 @@ from __future__ import annotations
 import torch
 
 
+def _check_offsets(offsets):
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise RuntimeError("seg['offsets'] must be int64 [R+1]")
+    return offsets
+
+
+def _choose_backend(backend, tensor, what, any_dtype=False):
+    """"hip" or "torch" from ``backend`` None, "hip" or "torch".  None is "hip" for a float32 CUDA ``tensor`` (for every
+    CUDA ``tensor`` with ``any_dtype``) and "torch" for everything else; "hip" takes a float32 CUDA ``tensor``."""
+    if backend not in (None, "hip", "torch"):
+        raise ValueError("backend must be None, 'hip' or 'torch'")
+    if backend is None:
+        backend = "hip" if tensor.is_cuda and (any_dtype or tensor.dtype == torch.float32) else "torch"
+    if backend == "hip" and (not tensor.is_cuda or tensor.dtype != torch.float32):
+        raise RuntimeError(f"the kernel takes float32 CUDA {what} (backend='torch' restates it for anything else)")
+    return backend
+
+
+def _entry_rays(offsets, total, dtype=torch.int64):
+    """[S]: the ray of every entry, on the device of ``offsets``."""
+    rays = torch.arange(offsets.numel() - 1, dtype=dtype, device=offsets.device)
+    return torch.repeat_interleave(rays, offsets[1:] - offsets[:-1], output_size=total)
+
+
+def _sums_in_ray(v, offsets, ray):
+    """The sum of ``v`` [S] over the ray's earlier entries [S], and over all of each ray's entries [R]: differences of
+    one cumulative sum over the whole list."""
+    run0 = torch.cat([v.new_zeros(1), torch.cumsum(v, 0)])         # run0[e] = sum of the entries before e
+    first = run0[offsets[:-1]]                                     # [R]: the sum in front of each ray's first entry
+    return run0[:-1] - first[ray], run0[offsets[1:]] - first
+
+
+def _times_for_kernel(ctx, dev, t_enter, t_exit):
+    """The times as the kernels read them (float32 [S] on ``dev``); ``ctx`` records what their gradients must match."""
+    ctx.times = tuple((t.dtype, t.device, t.shape) for t in (t_enter, t_exit))
+    return tuple(t.detach().to(dev).to(torch.float32).reshape(-1).contiguous() for t in (t_enter, t_exit))
+
+
+def _times_grads(ctx, grad_t_enter, grad_t_exit):
+    """The kernels' gradients of the times in the dtype, device and shape the caller's times had."""
+    return tuple(None if g is None else g.to(device).to(dtype).reshape(shape)
+                 for g, (dtype, device, shape) in zip((grad_t_enter, grad_t_exit), ctx.times))
+
+
 def composite_segments(seg, density: torch.Tensor, rgb: torch.Tensor) -> torch.Tensor:
     """rgba [R, 4] of the rays of ``seg`` (the dict ``Pipeline.trace_segments`` returns: ``offsets`` int64 [R+1],
     ``cells`` [S], ``t_enter`` / ``t_exit`` float32 [S]) for a per-cell ``density`` [N] and ``rgb`` [N, 3]:
@@ -41,31 +85,13 @@ def composite_segments(seg, density: torch.Tensor, rgb: torch.Tensor) -> torch.T
         raise RuntimeError("rgb must have the dtype and device of density")
     if density.dim() != 1 or rgb.dim() != 2 or rgb.size(-1) != 3 or rgb.size(0) != density.size(0):
         raise RuntimeError("expected density [N] and rgb [N, 3]")
-    dev, dtype = density.device, density.dtype
-    offsets = seg["offsets"].to(dev)
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
-        raise RuntimeError("seg['offsets'] must be int64 [R+1]")
+    dev = density.device
+    offsets = _check_offsets(seg["offsets"].to(dev))
     cells = seg["cells"].to(dev).to(torch.int64)
-    num_rays, total = offsets.numel() - 1, cells.numel()
+    total = cells.numel()
     if seg["t_enter"].numel() != total or seg["t_exit"].numel() != total:
         raise RuntimeError("seg['cells'], seg['t_enter'] and seg['t_exit'] must have one element per entry")
-    t_enter = seg["t_enter"].to(dev).to(torch.float64)
-    t_exit = seg["t_exit"].to(dev).to(torch.float64)
-    dt = torch.where(torch.isinf(t_exit), torch.zeros_like(t_exit), (t_exit - t_enter).clamp_min(0.0))
-
-    log_keep = -density[cells].to(torch.float64) * dt              # log(1 - alpha) of every entry
-    run = torch.cumsum(log_keep, 0)                                # inclusive, across ray boundaries
-    run0 = torch.cat([run.new_zeros(1), run])                      # run0[e] = sum of the entries before e
-    counts = offsets[1:] - offsets[:-1]
-    ray = torch.repeat_interleave(torch.arange(num_rays, device=dev), counts, output_size=total)
-    before = run0[offsets[:-1]]                                    # [R]: the sum in front of each ray's first entry
-    transmittance = torch.exp(run0[:-1] - before[ray])             # in front of every entry, within its ray
-    weight = transmittance * -torch.expm1(log_keep)
-
-    out = torch.zeros((num_rays, 4), dtype=torch.float64, device=dev)
-    colour = out[:, :3].index_add(0, ray, weight.unsqueeze(-1) * rgb[cells].to(torch.float64))
-    alpha = -torch.expm1(run0[offsets[1:]] - before)
-    return torch.cat([colour, alpha.unsqueeze(-1)], dim=-1).to(dtype)
+    return _composite_entries_torch(offsets, seg["t_enter"], seg["t_exit"], density[cells], rgb[cells])
 
 
 def _check_entries_inputs(seg, sigma, values):
@@ -75,9 +101,7 @@ def _check_entries_inputs(seg, sigma, values):
         raise RuntimeError("values must have the dtype and device of sigma")
     if sigma.dim() != 1 or values.dim() != 2 or values.size(-1) < 1:
         raise RuntimeError("expected sigma [S] and values [S, C] with C >= 1")
-    offsets = seg["offsets"]
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
-        raise RuntimeError("seg['offsets'] must be int64 [R+1]")
+    offsets = _check_offsets(seg["offsets"])
     total = sigma.size(0)
     if seg["t_enter"].numel() != total or seg["t_exit"].numel() != total or values.size(0) != total:
         raise RuntimeError("sigma, values, seg['t_enter'] and seg['t_exit'] must have one element (row) per entry")
@@ -85,26 +109,24 @@ def _check_entries_inputs(seg, sigma, values):
 
 
 def _composite_entries_torch(offsets, t_enter, t_exit, sigma, values):
-    """The definition with the operations of ``composite_segments``: float64 throughout, a segmented exclusive
-    cumulative sum for the transmittance, one ``index_add`` over the ray index.  Autograd differentiates it."""
+    """The definition, and ``composite_segments``: float64 throughout, a segmented exclusive cumulative sum for the
+    transmittance, one ``index_add`` over the ray index.  Autograd differentiates it.  ``offsets`` is on the device of
+    ``sigma``."""
     dev, dtype = sigma.device, sigma.dtype
     num_rays, total = offsets.numel() - 1, sigma.size(0)
     t_enter = t_enter.to(dev).to(torch.float64).reshape(-1)
     t_exit = t_exit.to(dev).to(torch.float64).reshape(-1)
     dt = torch.where(torch.isinf(t_exit), torch.zeros_like(t_exit), (t_exit - t_enter).clamp_min(0.0))
 
-    log_keep = -sigma.to(torch.float64) * dt                       # -x of every entry
-    run = torch.cumsum(log_keep, 0)                                # inclusive, across ray boundaries
-    run0 = torch.cat([run.new_zeros(1), run])                      # run0[e] = sum of the entries before e
-    counts = offsets[1:] - offsets[:-1]
-    ray = torch.repeat_interleave(torch.arange(num_rays, device=dev), counts, output_size=total)
-    before = run0[offsets[:-1]]                                    # [R]: the sum in front of each ray's first entry
-    transmittance = torch.exp(run0[:-1] - before[ray])             # in front of every entry, within its ray
+    log_keep = -sigma.to(torch.float64) * dt                       # -x = log(1 - alpha) of every entry
+    ray = _entry_rays(offsets, total)
+    log_before, log_ray = _sums_in_ray(log_keep, offsets, ray)
+    transmittance = torch.exp(log_before)                          # in front of every entry, within its ray
     weight = transmittance * -torch.expm1(log_keep)
 
     out = torch.zeros((num_rays, values.size(1)), dtype=torch.float64, device=dev)
     composited = out.index_add(0, ray, weight.unsqueeze(-1) * values.to(torch.float64))
-    alpha = -torch.expm1(run0[offsets[1:]] - before)
+    alpha = -torch.expm1(log_ray)
     return torch.cat([composited, alpha.unsqueeze(-1)], dim=-1).to(dtype)
 
 
@@ -123,10 +145,8 @@ class _CompositeEntries(torch.autograd.Function):
             raise RuntimeError("too many rays or channels for the kernel")
         offsets = offsets.to(dev).contiguous()
         sigma_c, values_c = sigma.detach().contiguous(), values.detach().contiguous()
-        t_enter_c = t_enter.detach().to(dev).to(torch.float32).reshape(-1).contiguous()
-        t_exit_c = t_exit.detach().to(dev).to(torch.float32).reshape(-1).contiguous()
+        t_enter_c, t_exit_c = _times_for_kernel(ctx, dev, t_enter, t_exit)
         ctx.save_for_backward(sigma_c, values_c, t_enter_c, t_exit_c, offsets)
-        ctx.times = tuple((t.dtype, t.device, t.shape) for t in (t_enter, t_exit))
         if num_rays == 0 or total == 0:
             return torch.zeros((num_rays, channels + 1), dtype=torch.float32, device=dev)
         out = torch.empty((num_rays, channels + 1), dtype=torch.float32, device=dev)     # every element is written
@@ -155,10 +175,7 @@ class _CompositeEntries(torch.autograd.Function):
                     num_rays, _ptr(offsets), total, _ptr(t_enter), _ptr(t_exit), _ptr(sigma), _ptr(values), channels,
                     _ptr(grad_out), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _stream_ptr(dev))
             _lib.check(rc)
-        for i, (dtype, device, shape) in zip((2, 3), ctx.times):
-            if grads[i] is not None:
-                grads[i] = grads[i].to(device).to(dtype).reshape(shape)
-        return grads[0], grads[1], grads[2], grads[3], None
+        return (grads[0], grads[1], *_times_grads(ctx, grads[2], grads[3]), None)
 
 
 def composite_entries(seg, sigma: torch.Tensor, values: torch.Tensor, backend=None) -> torch.Tensor:
@@ -188,17 +205,11 @@ def composite_entries(seg, sigma: torch.Tensor, values: torch.Tensor, backend=No
     autograd, on any device; no Python loop over rays.  ``offsets[-1] == S`` is checked on the torch path only, and
     there only when ``seg["offsets"]`` lives on the CPU: on the device the check would be a synchronisation the caller
     has not asked for.  (The kernels clamp every offset to 0 .. S instead.)"""
-    if backend not in (None, "hip", "torch"):
-        raise ValueError("backend must be None, 'hip' or 'torch'")
     num_rays, total = _check_entries_inputs(seg, sigma, values)
-    if backend is None:
-        backend = "hip" if sigma.is_cuda and sigma.dtype == torch.float32 else "torch"
-    if backend == "torch":
+    if _choose_backend(backend, sigma, "sigma and values") == "torch":
         if not seg["offsets"].is_cuda and int(seg["offsets"][-1]) != total:
             raise RuntimeError("seg['offsets'][-1] must be the number of entries")
         return _composite_entries_torch(seg["offsets"].to(sigma.device), seg["t_enter"], seg["t_exit"], sigma, values)
-    if not sigma.is_cuda or sigma.dtype != torch.float32:
-        raise RuntimeError("the kernel takes float32 CUDA sigma and values (backend='torch' restates it for anything else)")
     return _CompositeEntries.apply(sigma, values, seg["t_enter"], seg["t_exit"], seg["offsets"])
 
 
@@ -212,9 +223,7 @@ def _check_distortion_inputs(seg, sigma, s_enter, s_exit):
             raise RuntimeError("s_enter and s_exit must have the dtype and device of sigma")
     if sigma.dim() != 1 or (s_enter is not None and (s_enter.dim() != 1 or s_exit.dim() != 1)):
         raise RuntimeError("expected sigma [S], and s_enter [S] and s_exit [S] where given")
-    offsets = seg["offsets"]
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
-        raise RuntimeError("seg['offsets'] must be int64 [R+1]")
+    offsets = _check_offsets(seg["offsets"])
     total = sigma.size(0)
     if seg["t_enter"].numel() != total or seg["t_exit"].numel() != total or (
             s_enter is not None and (s_enter.size(0) != total or s_exit.size(0) != total)):
@@ -237,12 +246,10 @@ def _ray_distortion_torch(offsets, t_enter, t_exit, sigma, s_enter, s_exit):
     width = torch.where(infinite, zero, (b - a).clamp_min(0.0))
 
     x = sigma.to(torch.float64) * dt
-    counts = offsets[1:] - offsets[:-1]
-    ray = torch.repeat_interleave(torch.arange(num_rays, device=dev), counts, output_size=total)
+    ray = _entry_rays(offsets, total)
 
     def before(v):                                                 # the sum of v over the ray's earlier entries
-        run0 = torch.cat([v.new_zeros(1), torch.cumsum(v, 0)])     # run0[e] = sum of the entries before e
-        return run0[:-1] - run0[offsets[:-1]][ray]
+        return _sums_in_ray(v, offsets, ray)[0]
 
     weight = torch.exp(-before(x)) * -torch.expm1(-x)
     per_entry = 2 * weight * (mid * before(weight) - before(weight * mid)) + weight * weight * width / 3
@@ -264,14 +271,12 @@ class _RayDistortion(torch.autograd.Function):
             raise RuntimeError("too many rays for the kernel")
         offsets = offsets.to(dev).contiguous()
         sigma_c = sigma.detach().contiguous()
-        t_enter_c = t_enter.detach().to(dev).to(torch.float32).reshape(-1).contiguous()
-        t_exit_c = t_exit.detach().to(dev).to(torch.float32).reshape(-1).contiguous()
+        t_enter_c, t_exit_c = _times_for_kernel(ctx, dev, t_enter, t_exit)
         ctx.own_measure = s_enter is not None
         saved = [sigma_c, t_enter_c, t_exit_c, offsets]
         if ctx.own_measure:
             saved += [s_enter.detach().contiguous(), s_exit.detach().contiguous()]
         ctx.save_for_backward(*saved)
-        ctx.times = tuple((t.dtype, t.device, t.shape) for t in (t_enter, t_exit))
         if num_rays == 0 or total == 0:
             return torch.zeros(num_rays, dtype=torch.float32, device=dev)
         out = torch.empty(num_rays, dtype=torch.float32, device=dev)                     # every element is written
@@ -303,10 +308,7 @@ class _RayDistortion(torch.autograd.Function):
                     _ptr(measure[1]), _ptr(grad_out), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]),
                     _ptr(grads[4]), _stream_ptr(dev))
             _lib.check(rc)
-        for i, (dtype, device, shape) in zip((1, 2), ctx.times):
-            if grads[i] is not None:
-                grads[i] = grads[i].to(device).to(dtype).reshape(shape)
-        return grads[0], grads[1], grads[2], grads[3], grads[4], None
+        return (grads[0], *_times_grads(ctx, grads[1], grads[2]), grads[3], grads[4], None)
 
 
 def ray_distortion(seg, sigma: torch.Tensor, s_enter=None, s_exit=None, backend=None) -> torch.Tensor:
@@ -344,18 +346,12 @@ def ray_distortion(seg, sigma: torch.Tensor, s_enter=None, s_exit=None, backend=
     sums, differentiated by autograd, on any device; no Python loop over rays.  ``offsets[-1] == S`` is checked on the
     torch path only, and there only when ``seg["offsets"]`` lives on the CPU.  (The kernels clamp every offset to
     0 .. S instead.)"""
-    if backend not in (None, "hip", "torch"):
-        raise ValueError("backend must be None, 'hip' or 'torch'")
     num_rays, total = _check_distortion_inputs(seg, sigma, s_enter, s_exit)
-    if backend is None:
-        backend = "hip" if sigma.is_cuda and sigma.dtype == torch.float32 else "torch"
-    if backend == "torch":
+    if _choose_backend(backend, sigma, "sigma") == "torch":
         if not seg["offsets"].is_cuda and int(seg["offsets"][-1]) != total:
             raise RuntimeError("seg['offsets'][-1] must be the number of entries")
         return _ray_distortion_torch(seg["offsets"].to(sigma.device), seg["t_enter"], seg["t_exit"], sigma, s_enter,
                                      s_exit)
-    if not sigma.is_cuda or sigma.dtype != torch.float32:
-        raise RuntimeError("the kernel takes float32 CUDA sigma (backend='torch' restates it for anything else)")
     return _RayDistortion.apply(sigma, seg["t_enter"], seg["t_exit"], s_enter, s_exit, seg["offsets"])
 
 
@@ -367,9 +363,7 @@ def _check_segment_grad_inputs(seg, exit_cells, points, rays, grad_t_enter, grad
         raise RuntimeError("expected points [N, 3]")
     if points.dtype not in (torch.float32, torch.float64):
         raise RuntimeError("points must have float32 or float64 dtype")
-    offsets = seg["offsets"]
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
-        raise RuntimeError("seg['offsets'] must be int64 [R+1]")
+    offsets = _check_offsets(seg["offsets"])
     num_rays, total = offsets.numel() - 1, seg["cells"].numel()
     if seg["t_enter"].numel() != total or seg["t_exit"].numel() != total:
         raise RuntimeError("seg['cells'], seg['t_enter'] and seg['t_exit'] must have one element per entry")
@@ -390,8 +384,7 @@ def _segment_face_totals(seg, exit_cells, dev, dtype, grad_t_enter, grad_t_exit,
     t_enter, t_exit = seg["t_enter"].to(dev), seg["t_exit"].to(dev)      # holders: from the stored floats
     g_enter, g_exit = grad_t_enter.to(dev).to(dtype).reshape(-1), grad_t_exit.to(dev).to(dtype).reshape(-1)
     exits = exit_cells.to(dev).to(torch.int64) & _NONE
-    counts = offsets[1:] - offsets[:-1]
-    ray = torch.repeat_interleave(torch.arange(num_rays, device=dev), counts, output_size=total)
+    ray = _entry_rays(offsets, total)
     index = torch.arange(total, device=dev)
 
     # the cell behind face j: the next entry, or exit_cells behind a ray's last entry; none behind an infinite exit
@@ -482,16 +475,9 @@ def segment_points_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit
     CUDA tensors go through the HIP kernel (float32 points; one lane per entry, atomics into a zeroed [N, 3]).  CPU
     tensors, and CUDA tensors with ``backend="torch"``, go through a vectorised torch restatement in the dtype of
     ``points`` (float32 or float64): no Python loop over rays."""
-    if backend not in (None, "hip", "torch"):
-        raise ValueError("backend must be None, 'hip' or 'torch'")
     num_rays, total = _check_segment_grad_inputs(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit)
-    if backend is None:
-        backend = "hip" if points.is_cuda else "torch"
-    if backend == "torch":
+    if _choose_backend(backend, points, "points", any_dtype=True) == "torch":
         return _segment_points_grad_torch(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, num_rays, total)
-
-    if not points.is_cuda or points.dtype != torch.float32:
-        raise RuntimeError("the kernel takes float32 CUDA points (backend='torch' restates it for anything else)")
     out = torch.zeros((points.size(0), 3), dtype=torch.float32, device=points.device)
     return _segment_grad_hip("rf_segments_points_grad", out, seg, exit_cells, points, rays, grad_t_enter, grad_t_exit,
                              num_rays, total)
@@ -520,8 +506,7 @@ def _segment_grad_hip(symbol, out, seg, exit_cells, points, rays, grad_t_enter, 
         raise RuntimeError("seg['cells'] and exit_cells must have uint32 dtype")
     t_enter, t_exit = f32(seg["t_enter"]), f32(seg["t_exit"])
     g_enter, g_exit = f32(grad_t_enter), f32(grad_t_exit)
-    counts = offsets[1:] - offsets[:-1]
-    entry_ray = torch.repeat_interleave(torch.arange(num_rays, dtype=torch.int32, device=dev), counts, output_size=total)
+    entry_ray = _entry_rays(offsets, total, dtype=torch.int32)
     with torch.cuda.device(dev):
         rc = getattr(_lib.load(), symbol)(
             points_c.size(0), _ptr(points_c), num_rays, _ptr(rays_c), _ptr(offsets), total, _ptr(entry_ray),
@@ -548,15 +533,9 @@ def segment_rays_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, 
     the wave, one atomic update of a ray's row per wave the ray reaches into).  CPU tensors, and CUDA tensors with
     ``backend="torch"``, go through a vectorised torch restatement in the dtype of ``points`` (float32 or float64): no
     Python loop over rays."""
-    if backend not in (None, "hip", "torch"):
-        raise ValueError("backend must be None, 'hip' or 'torch'")
     num_rays, total = _check_segment_grad_inputs(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit)
-    if backend is None:
-        backend = "hip" if points.is_cuda else "torch"
-    if backend == "torch":
+    if _choose_backend(backend, points, "points", any_dtype=True) == "torch":
         return _segment_rays_grad_torch(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, num_rays, total)
-    if not points.is_cuda or points.dtype != torch.float32:
-        raise RuntimeError("the kernel takes float32 CUDA points (backend='torch' restates it for anything else)")
     out = torch.zeros((num_rays, 6), dtype=torch.float32, device=points.device)
     return _segment_grad_hip("rf_segments_rays_grad", out, seg, exit_cells, points, rays, grad_t_enter, grad_t_exit,
                              num_rays, total)
