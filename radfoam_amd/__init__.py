@@ -10,7 +10,7 @@ package ``radfoam/`` at the repo root.
 from .geometry import CellGeometry, cell_geometry, cell_geometry_grad, cell_surface, differentiable_cell_geometry
 from .pipeline import Pipeline, create_pipeline, invalidate_caches
 from .scene_ops import pack_attributes
-from .segments import (composite_entries, composite_segments, ray_distortion, segment_points_grad,
+from .segments import (composite_entries, composite_segments, ray_distortion, ray_quantiles, segment_points_grad,
                        segment_rays_grad)
 from .shims import (BatchFetcher, Triangulation, TriangulationFailedError, Viewer, build_aabb_tree,
                     farthest_neighbor, nn, run_with_viewer)
@@ -20,5 +20,5 @@ __all__ = [
     "nn", "farthest_neighbor", "BatchFetcher", "Viewer", "run_with_viewer", "pack_attributes",
     "invalidate_caches", "CellGeometry", "cell_geometry", "cell_surface", "composite_segments",
     "segment_points_grad", "segment_rays_grad", "composite_entries", "cell_geometry_grad",
-    "differentiable_cell_geometry", "ray_distortion",
+    "differentiable_cell_geometry", "ray_distortion", "ray_quantiles",
 ]

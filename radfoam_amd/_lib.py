@@ -65,7 +65,7 @@ class LaunchOpts(C.Structure):
 
 
 # every symbol include/radfoam_hip.h, radfoam_hip_geometry.h, radfoam_hip_geometry_grad.h, radfoam_hip_segments.h,
-# radfoam_hip_composite.h and radfoam_hip_distortion.h declare:
+# radfoam_hip_composite.h, radfoam_hip_distortion.h and radfoam_hip_quantiles.h declare:
 # name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -133,6 +133,10 @@ SYMBOLS = {
     "rf_distortion_rays_per_wave": (_U32, []),
     "rf_ray_distortion_forward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "rf_ray_distortion_backward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rf_quantiles_rays_per_wave": (_U32, []),
+    "rf_quantiles_max": (_U32, []),
+    "rf_ray_quantiles_forward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _U32, _P, _P, _P, _P]),
+    "rf_ray_quantiles_backward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

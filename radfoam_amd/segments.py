@@ -11,7 +11,9 @@ device, vectorised torch restatements of the same definitions elsewhere (DESIGN 
 ``composite_entries`` is the same compositing for inputs the caller has per ENTRY (a density [S] and any number of
 channels [S, C]), with kernels of its own for float32 tensors on the device (rf_composite.hip).
 ``ray_distortion`` is the regulariser that goes with it: Mip-NeRF 360's distortion loss of every ray from the same
-per-entry density, by the same scheme of kernels (rf_distortion.hip).
+per-entry density, by the same scheme of kernels (rf_distortion.hip).  ``ray_quantiles`` is the depth
+output: where along the ray the transmittance of that density falls through given levels (rf_quantiles.hip, DESIGN
+4.14).
 """
 from __future__ import annotations
 
@@ -353,6 +355,165 @@ def ray_distortion(seg, sigma: torch.Tensor, s_enter=None, s_exit=None, backend=
         return _ray_distortion_torch(seg["offsets"].to(sigma.device), seg["t_enter"], seg["t_exit"], sigma, s_enter,
                                      s_exit)
     return _RayDistortion.apply(sigma, seg["t_enter"], seg["t_exit"], s_enter, s_exit, seg["offsets"])
+
+
+def _check_quantiles_inputs(seg, sigma, quantiles):
+    if sigma.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("sigma must have float32 or float64 dtype")
+    if quantiles.dtype != sigma.dtype or quantiles.device != sigma.device:
+        raise RuntimeError("quantiles must have the dtype and device of sigma")
+    if sigma.dim() != 1 or quantiles.dim() < 1 or quantiles.size(-1) < 1:
+        raise RuntimeError("expected sigma [S] and quantiles [R, Q] with Q >= 1")
+    offsets = _check_offsets(seg["offsets"])
+    num_rays, total, num_q = offsets.numel() - 1, sigma.size(0), quantiles.size(-1)
+    if seg["t_enter"].numel() != total or seg["t_exit"].numel() != total:
+        raise RuntimeError("sigma, seg['t_enter'] and seg['t_exit'] must have one element per entry")
+    if quantiles.numel() != num_rays * num_q:
+        raise RuntimeError("quantiles must have one row of Q per ray")
+    return num_rays, total, num_q
+
+
+def _quantile_levels(quantiles, num_rays, num_q):
+    """[R, Q] float64: L = max(-log q, 0), and +inf (never reached) where q <= 0 or q is NaN.  Both backends compare
+    against these very bits, so they cannot disagree on the entry a quantile falls in because of a logarithm."""
+    q = quantiles.detach().to(torch.float64).reshape(num_rays, num_q)
+    never = (q <= 0) | torch.isnan(q)
+    level = (-torch.log(torch.where(never, torch.ones_like(q), q))).clamp_min(0.0)
+    return torch.where(never, torch.full_like(q, float("inf")), level).contiguous()
+
+
+def _ray_quantiles_torch(offsets, t_enter, t_exit, sigma, levels):
+    """The definition: float64 throughout, one cumulative sum of x over the whole list, per quantile one
+    ``searchsorted`` for the sum in front of the ray plus the level, gathers for t_enter[j], X_j and sigma[j].  Autograd
+    differentiates it.  ``offsets`` and ``levels`` are on the device of ``sigma``."""
+    dev, dtype = sigma.device, sigma.dtype
+    total = sigma.size(0)
+    if total == 0:
+        return (torch.full(levels.shape, -1.0, dtype=dtype, device=dev),
+                torch.full(levels.shape, -1, dtype=torch.int64, device=dev))
+    t_enter = t_enter.to(dev).to(torch.float64).reshape(-1)
+    t_exit = t_exit.to(dev).to(torch.float64).reshape(-1)
+    dt = torch.where(torch.isinf(t_exit), torch.zeros_like(t_exit), (t_exit - t_enter).clamp_min(0.0))
+    density = sigma.to(torch.float64)
+    x = density * dt
+    run0 = torch.cat([x.new_zeros(1), torch.cumsum(x, 0)])         # run0[e] = sum of the entries before e
+    first = run0[offsets[:-1]].unsqueeze(-1)                       # [R, 1]: the sum in front of each ray's first entry
+    # the first entry whose inclusive sum exceeds first + L: at or behind the ray's first entry, as L >= 0
+    j = torch.searchsorted(run0.detach()[1:].contiguous(), (first.detach() + levels).contiguous(), right=True)
+    valid = j < offsets[1:].unsqueeze(-1)
+    at = torch.where(valid, j, torch.zeros_like(j))
+    # selected before the division: a pair without a crossing divides 0 by 1, and no 0 * inf reaches a gradient
+    remaining = torch.where(valid, levels - (run0[at] - first), torch.zeros_like(levels))
+    density_at = torch.where(valid, density[at], torch.ones_like(levels))
+    depth = torch.where(valid, t_enter[at] + remaining / density_at, torch.full_like(levels, -1.0))
+    return depth.to(dtype), torch.where(valid, j, torch.full_like(j, -1))
+
+
+class _RayQuantiles(torch.autograd.Function):
+    """``ray_quantiles`` through the kernels of rf_quantiles.hip: float32 CUDA tensors, each gradient only where its
+    input needs one.  The inputs, the levels and the entries of the forward are kept for the backward, which sweeps the
+    list once more."""
+
+    @staticmethod
+    def forward(ctx, sigma, t_enter, t_exit, levels, offsets):
+        from . import _lib
+        from .pipeline import _ptr, _stream_ptr
+
+        dev = sigma.device
+        num_rays, total, num_q = offsets.numel() - 1, sigma.size(0), levels.size(1)
+        if num_rays >= 2 ** 31:
+            raise RuntimeError("too many rays for the kernel")
+        offsets = offsets.to(dev).contiguous()
+        sigma_c = sigma.detach().contiguous()
+        t_enter_c, t_exit_c = _times_for_kernel(ctx, dev, t_enter, t_exit)
+        if num_rays == 0 or total == 0:
+            depth = torch.full((num_rays, num_q), -1.0, dtype=torch.float32, device=dev)
+            entries = torch.full((num_rays, num_q), -1, dtype=torch.int64, device=dev)
+        else:
+            depth = torch.empty((num_rays, num_q), dtype=torch.float32, device=dev)      # every element is written
+            entries = torch.empty((num_rays, num_q), dtype=torch.int64, device=dev)
+            with torch.cuda.device(dev):
+                rc = _lib.load().rf_ray_quantiles_forward(
+                    num_rays, _ptr(offsets), total, _ptr(t_enter_c), _ptr(t_exit_c), _ptr(sigma_c), num_q,
+                    _ptr(levels), _ptr(depth), _ptr(entries), _stream_ptr(dev))
+            _lib.check(rc)
+        ctx.save_for_backward(sigma_c, t_enter_c, t_exit_c, offsets, levels, entries)
+        ctx.mark_non_differentiable(entries)
+        return depth, entries
+
+    @staticmethod
+    def backward(ctx, grad_depth, _grad_entries):
+        from . import _lib
+        from .pipeline import _ptr, _stream_ptr
+
+        sigma, t_enter, t_exit, offsets, levels, entries = ctx.saved_tensors
+        dev = sigma.device
+        num_rays, total, num_q = offsets.numel() - 1, sigma.size(0), levels.size(1)
+        want = ctx.needs_input_grad[:3]
+        # entries outside offsets[0] .. offsets[R] are not written by the kernel: there are none in a sound list
+        grads = [torch.empty_like(sigma) if w else None for w in want]
+        if num_rays > 0 and total > 0 and any(want):
+            grad_depth = grad_depth.to(torch.float32).contiguous()
+            with torch.cuda.device(dev):
+                rc = _lib.load().rf_ray_quantiles_backward(
+                    num_rays, _ptr(offsets), total, _ptr(t_enter), _ptr(t_exit), _ptr(sigma), num_q, _ptr(levels),
+                    _ptr(entries), _ptr(grad_depth), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _stream_ptr(dev))
+            _lib.check(rc)
+        return (grads[0], *_times_grads(ctx, grads[1], grads[2]), None, None)
+
+
+def ray_quantiles(seg, sigma: torch.Tensor, quantiles: torch.Tensor, backend=None):
+    """(depth [R, Q], entries [R, Q] int64): where along each ray of ``seg`` (the dict ``Pipeline.trace_segments`` or
+    ``trace_differentiable_segments`` returns; ``offsets`` int64 [R+1] and ``t_enter`` / ``t_exit`` [S] are read,
+    ``cells`` is not) the transmittance of a density ``sigma`` [S] PER ENTRY, float32 or float64, falls through the
+    levels ``quantiles`` [R, Q] (any shape with R Q elements whose last dimension is Q; dtype and device of ``sigma``):
+    the ``depth`` output of ``trace_forward(depth_quantiles=...)`` for a density of one's own.  q = 0.5 is the median
+    depth; ``|depth[:, 0] - depth[:, 1]|`` on two random quantiles is the reference's regulariser
+    (examples/quantile_regulariser.py); ``seg["cells"][entries]`` are the reference's ``quantile_point_indices``.  Per
+    ray, over its entries in order, in double:
+
+        dt = 0 where t_exit is infinite, else max(t_exit - t_enter, 0),      x = sigma dt
+        X_i = sum of x over the ray's earlier entries,      I_i = X_i + x_i
+        L = max(-log(quantile), 0);  +inf (never reached) where the quantile is <= 0 or NaN
+        j = the first entry of the ray with I_j > L
+        depth = t_enter[j] + (L - X_j) / sigma[j],      entries = j, an index into the list
+
+    and depth = -1, entries = -1 where the ray has no such entry: the quantile lies below the ray's final
+    transmittance, or the ray has no entries.  Every quantile is found on its own; for a row sorted in descending order
+    this is what the reference's sequential loop gives.  A quantile >= 1 behaves as 1: its depth is ``t_enter`` of the
+    first entry with x > 0.  ``sigma >= 0`` is a precondition (negative densities give unspecified values).  The result
+    has the dtype of ``sigma``.
+
+    Differentiable in ``sigma``, ``seg["t_enter"]`` and ``seg["t_exit"]`` (which carry the gradient on to the points and
+    the rays when they come from ``trace_differentiable_segments``), not in ``quantiles``; ``entries`` is marked
+    non-differentiable.  The entry a quantile falls in is held fixed.  The times' gradient follows torch's
+    ``clamp_min``: an entry with t_exit >= t_enter, both finite, passes it on; an entry with an infinite t_exit gets
+    exact zeros in every gradient; ``t_exit`` of the crossing entry gets nothing.
+
+    ``backend``: None, "hip" or "torch", as in ``composite_entries``.  None is "hip" for float32 CUDA ``sigma`` with at
+    most ``rf_quantiles_max()`` (8) quantiles per ray and "torch" for everything else; "hip" with more quantiles raises.
+    "hip" runs the kernels of rf_quantiles.hip (one wave owns a run of consecutive rays, a segmented scan in double, one
+    rounding to float32, no atomics: the same bits from call to call, gradients included; the times are read as
+    float32).  "torch" restates the definition in float64 with one list-wide cumulative sum and a ``searchsorted`` per
+    quantile, differentiated by autograd, on any device; no Python loop over rays.  The levels L are formed here, in
+    float64, for both backends.  ``offsets[-1] == S`` is checked on the torch path only, and there only when
+    ``seg["offsets"]`` lives on the CPU.  (The kernels clamp every offset to 0 .. S instead.)"""
+    num_rays, total, num_q = _check_quantiles_inputs(seg, sigma, quantiles)
+    chosen = _choose_backend(backend, sigma, "sigma")
+    if chosen == "hip":
+        from . import _lib
+
+        most = int(_lib.load().rf_quantiles_max())
+        if num_q > most and backend is None:
+            chosen = "torch"
+        elif num_q > most:
+            raise RuntimeError(f"the kernel takes at most {most} quantiles per ray (backend='torch' takes any number)")
+    levels = _quantile_levels(quantiles, num_rays, num_q)
+    if chosen == "torch":
+        if not seg["offsets"].is_cuda and int(seg["offsets"][-1]) != total:
+            raise RuntimeError("seg['offsets'][-1] must be the number of entries")
+        return _ray_quantiles_torch(seg["offsets"].to(sigma.device), seg["t_enter"], seg["t_exit"], sigma, levels)
+    return _RayQuantiles.apply(sigma, seg["t_enter"], seg["t_exit"], levels, seg["offsets"])
 
 
 _NONE = 0xFFFFFFFF
