@@ -7,6 +7,7 @@ include/radfoam_hip.h; everything else the reference module exports is a torch/s
 (radfoam_amd/shims.py).  ``import radfoam`` resolves to this package through the alias
 package ``radfoam/`` at the repo root.
 """
+from .cells import CellEntries, cell_entries, gather_cells, reduce_entries
 from .geometry import CellGeometry, cell_geometry, cell_geometry_grad, cell_surface, differentiable_cell_geometry
 from .pipeline import Pipeline, create_pipeline, invalidate_caches
 from .scene_ops import pack_attributes
@@ -20,5 +21,6 @@ __all__ = [
     "nn", "farthest_neighbor", "BatchFetcher", "Viewer", "run_with_viewer", "pack_attributes",
     "invalidate_caches", "CellGeometry", "cell_geometry", "cell_surface", "composite_segments",
     "segment_points_grad", "segment_rays_grad", "composite_entries", "cell_geometry_grad",
-    "differentiable_cell_geometry", "ray_distortion", "ray_quantiles",
+    "differentiable_cell_geometry", "ray_distortion", "ray_quantiles", "CellEntries", "cell_entries",
+    "gather_cells", "reduce_entries",
 ]

@@ -1,5 +1,6 @@
 // rf_ray_sweep.hpp -- the wave scheme of the kernels that go over an exported walk ray by ray (rf_composite.hip,
-// rf_distortion.hip), and the 64-bit lane exchange (also rf_segments_rays_grad.hip).
+// rf_distortion.hip, rf_quantiles.hip), and the 64-bit lane exchange and the segmented scan over
+// a wave, which other kernels use without the rays (rf_segments_rays_grad.hip, rf_cell_reduce.hip).
 //
 // ONE WAVE OWNS kRays CONSECUTIVE RAYS and sweeps their contiguous range of entries 64 at a time, one lane per entry,
 // from the 64-aligned entry at or below the range's first: every [S] array is read coalesced.  No ray is shared between
@@ -29,7 +30,7 @@
 
 namespace rf {
 
-// 64-bit values across the lanes of a wave
+// 64-bit values across the lanes of a wave, and sums of doubles over runs of lanes
 struct WaveLanes {
     // the value lane `src` (0 .. 63) holds, every lane of the wave taking part
     static __device__ __forceinline__ uint64_t bits_from_lane(uint64_t bits, int src) {
@@ -55,6 +56,24 @@ struct WaveLanes {
         const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)x);
         const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
         return (int64_t)(((uint64_t)hi << 32) | (uint64_t)lo);
+    }
+
+    // inclusive segmented scan over the wave (begin: the first lane of the lane's run): after the step of distance s a
+    // lane holds the sum over max(begin, lane - 2s + 1) .. lane.  The source index wraps below lane 0; what comes from
+    // there is not added.
+    template <int N>
+    static __device__ __forceinline__ void scan(double (&v)[N], int lane, int begin) {
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const int src = (lane - s) & 63;
+            double u[N];
+#pragma unroll
+            for (int n = 0; n < N; ++n) u[n] = from_lane(v[n], src);
+            if (lane - s >= begin) {
+#pragma unroll
+                for (int n = 0; n < N; ++n) v[n] = v[n] + u[n];
+            }
+        }
     }
 };
 
@@ -130,23 +149,6 @@ struct RaySweep : WaveLanes {
         s.ends = s.valid && seg_hi <= step_end;
         s.last = s.valid && w.lane == end;
         return s;
-    }
-
-    // inclusive segmented scan over the wave: after the step of distance s a lane holds the sum over
-    // max(begin, lane - 2s + 1) .. lane.  The source index wraps below lane 0; what comes from there is not added.
-    template <int N>
-    static __device__ __forceinline__ void scan(double (&v)[N], int lane, int begin) {
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const int src = (lane - s) & 63;
-            double u[N];
-#pragma unroll
-            for (int n = 0; n < N; ++n) u[n] = from_lane(v[n], src);
-            if (lane - s >= begin) {
-#pragma unroll
-                for (int n = 0; n < N; ++n) v[n] = v[n] + u[n];
-            }
-        }
     }
 
     // what the ray that runs past the step's last lane hands on: every lane gets it (0 when no ray does)
