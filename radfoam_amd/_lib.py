@@ -65,7 +65,8 @@ class LaunchOpts(C.Structure):
 
 
 # every symbol include/radfoam_hip.h, radfoam_hip_geometry.h, radfoam_hip_geometry_grad.h, radfoam_hip_segments.h,
-# radfoam_hip_composite.h, radfoam_hip_distortion.h, radfoam_hip_quantiles.h and radfoam_hip_cell_reduce.h declare:
+# radfoam_hip_composite.h, radfoam_hip_distortion.h, radfoam_hip_quantiles.h, radfoam_hip_cell_reduce.h and
+# radfoam_hip_sh_entries.h declare:
 # name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -140,6 +141,13 @@ SYMBOLS = {
     "rf_reduce_entries_chunk": (_U32, []),
     "rf_reduce_entries_workspace_bytes": (C.c_size_t, [C.c_int64, _U32]),
     "rf_reduce_entries": (_INT, [C.c_int64, C.c_int64, _P, _P, _P, _U32, _P, _P, C.c_size_t, _P]),
+    "rf_sh_entries_group": (_U32, []),
+    "rf_sh_entries_forward": (_INT, [_U32, C.c_int64, C.c_int64, _U32, _P, _P, _P, _U32, _P, _P, _P]),
+    "rf_sh_entries_workspace_bytes": (C.c_size_t, [C.c_int64, _U32]),
+    "rf_sh_entries_backward_coeffs": (_INT, [_U32, C.c_int64, C.c_int64, _U32, _P, _P, _P, _P, _P, _P, _P, _P,
+                                             C.c_size_t, _P]),
+    "rf_sh_entries_backward_directions": (_INT, [_U32, C.c_int64, C.c_int64, _U32, _P, _P, _P, _U32, _P, _P, _P, _P,
+                                                 _P]),
 }
 
 _lib = None
