@@ -42,7 +42,8 @@ def _oracle_walk(fm, rays, start, cap=512):
     if counts.max(initial=0) > cap:
         raise RuntimeError("a ray of this frame scans more cells than the oracle was asked to record")
     keep = np.arange(cap)[None, :] < counts[:, None]
-    t_enter = np.concatenate([np.zeros((len(n), 1), np.float32), np.maximum.accumulate(t_exit, axis=1)[:, :-1]], axis=1)
+    # the compositing's t0: the running maximum of 0 and the earlier exits (a first exit may be negative)
+    t_enter = np.fmax.accumulate(np.concatenate([np.zeros((len(n), 1), np.float32), t_exit], axis=1), axis=1)[:, :-1]
     seg = {"offsets": torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)),
            "cells": torch.from_numpy(cells[keep].astype(np.int64)), "t_enter": torch.from_numpy(t_enter[keep]),
            "t_exit": torch.from_numpy(t_exit[keep])}

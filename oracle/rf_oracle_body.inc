@@ -187,7 +187,8 @@ static inline uint32_t SUF(bit_distance)(float a, float b) {
 
 /* offset of entry q of the cell's list PADDED to a multiple of four, as the kernels' face tables hold it: real faces as
  * they are; padding = the first entry of the block times 2^(position in the block), zero if that leaves fp16 (pad_offset,
- * rf_kernels.hip) */
+ * rf_kernels.hip; the kernels' side of that branch runs on the scaled_2p13 / scaled_2p14 foams of
+ * tests/test_gpu_foam_zoo.py) */
 static inline void SUF(padded_offset)(const SUF(foam_t) *fm, uint32_t b, uint32_t cnt, uint32_t q, float *o) {
     if (q < cnt) {
         for (int i = 0; i < 3; ++i) o[i] = h2f(fm->diff[4 * (size_t)(b + q) + i]);

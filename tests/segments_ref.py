@@ -10,12 +10,14 @@ _CASES = {}
 
 def to_csr(cells, t1, n, max_intersections=1024):
     """Padded [R, cap] arrays of oracle.trace_paths -> dict of numpy arrays (offsets, cells, t_exit, t_enter, n).
-    t_enter is the float32 running maximum of the earlier t_exit with a leading 0."""
+    t_enter is the t0 the oracle's compositing used (t0 = 0, then t0 = max(t0, t_exit) after every cell): the float32
+    running maximum of 0 and the earlier t_exit -- 0, not the exit, behind a first exit that is negative (a ray whose
+    origin lies a rounding outside its start cell: tests/foam_zoo.py has such rays far from the world origin)."""
     r, cap = t1.shape
     counts = np.minimum(n.astype(np.int64), max_intersections)
     assert counts.max(initial=0) <= cap, "oracle cap too small for this case"
     keep = np.arange(cap)[None, :] < counts[:, None]
-    t_enter = np.concatenate([np.zeros((r, 1), np.float32), np.maximum.accumulate(t1, axis=1)[:, :-1]], axis=1)
+    t_enter = np.fmax.accumulate(np.concatenate([np.zeros((r, 1), np.float32), t1], axis=1), axis=1)[:, :-1]
     assert t_enter.dtype == np.float32
     return {"offsets": np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), "cells": cells[keep],
             "t_exit": t1[keep], "t_enter": t_enter[keep], "n": n.astype(np.uint32), "counts": counts}
