@@ -11,8 +11,8 @@ from .cells import CellEntries, cell_entries, gather_cells, reduce_entries
 from .geometry import CellGeometry, cell_geometry, cell_geometry_grad, cell_surface, differentiable_cell_geometry
 from .pipeline import Pipeline, create_pipeline, invalidate_caches
 from .scene_ops import pack_attributes
-from .segments import (composite_entries, composite_segments, ray_distortion, ray_quantiles, segment_points_grad,
-                       segment_rays_grad)
+from .segments import (composite_entries, composite_segments, entry_weights, ray_distortion, ray_quantiles,
+                       segment_points_grad, segment_rays_grad)
 from .sh_entries import sh_entries
 from .shims import (BatchFetcher, Triangulation, TriangulationFailedError, Viewer, build_aabb_tree,
                     farthest_neighbor, nn, run_with_viewer)
@@ -23,5 +23,5 @@ __all__ = [
     "invalidate_caches", "CellGeometry", "cell_geometry", "cell_surface", "composite_segments",
     "segment_points_grad", "segment_rays_grad", "composite_entries", "cell_geometry_grad",
     "differentiable_cell_geometry", "ray_distortion", "ray_quantiles", "CellEntries", "cell_entries",
-    "gather_cells", "reduce_entries", "sh_entries",
+    "gather_cells", "reduce_entries", "sh_entries", "entry_weights",
 ]

@@ -65,8 +65,8 @@ class LaunchOpts(C.Structure):
 
 
 # every symbol include/radfoam_hip.h, radfoam_hip_geometry.h, radfoam_hip_geometry_grad.h, radfoam_hip_segments.h,
-# radfoam_hip_composite.h, radfoam_hip_distortion.h, radfoam_hip_quantiles.h, radfoam_hip_cell_reduce.h and
-# radfoam_hip_sh_entries.h declare:
+# radfoam_hip_composite.h, radfoam_hip_distortion.h, radfoam_hip_quantiles.h, radfoam_hip_cell_reduce.h,
+# radfoam_hip_sh_entries.h and radfoam_hip_entry_weights.h declare:
 # name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -148,6 +148,9 @@ SYMBOLS = {
                                              C.c_size_t, _P]),
     "rf_sh_entries_backward_directions": (_INT, [_U32, C.c_int64, C.c_int64, _U32, _P, _P, _P, _U32, _P, _P, _P, _P,
                                                  _P]),
+    "rf_entry_weights_rays_per_wave": (_U32, []),
+    "rf_entry_weights_forward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "rf_entry_weights_backward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

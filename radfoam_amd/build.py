@@ -21,7 +21,8 @@ HEADERS = [os.path.join(_CSRC, n) for n in ("rf_math.hpp", "rf_foam.hpp", "rf_wa
 EXTRA_SOURCES = [os.path.join(_CSRC, n) for n in ("rf_cell_geometry.hip", "rf_segments.hip", "rf_segments_grad.hip",
                                                       "rf_segments_rays_grad.hip", "rf_composite.hip",
                                                       "rf_cell_geometry_grad.hip", "rf_distortion.hip",
-                                                      "rf_quantiles.hip", "rf_cell_reduce.hip", "rf_sh_entries.hip")]
+                                                      "rf_quantiles.hip", "rf_cell_reduce.hip", "rf_sh_entries.hip",
+                                                      "rf_entry_weights.hip")]
 EXTRA_HEADERS = [os.path.join(_CSRC, n) for n in ("rf_clip.hpp", "rf_clip_grad.hpp", "rf_ray_sweep.hpp",
                                                       "rf_segments_face.hpp")] + [
     os.path.join(os.path.dirname(_HERE), "include", n) for n in ("radfoam_hip_geometry.h", "radfoam_hip_segments.h",
@@ -30,7 +31,8 @@ EXTRA_HEADERS = [os.path.join(_CSRC, n) for n in ("rf_clip.hpp", "rf_clip_grad.h
                                                                "radfoam_hip_distortion.h",
                                                                "radfoam_hip_quantiles.h",
                                                                "radfoam_hip_cell_reduce.h",
-                                                               "radfoam_hip_sh_entries.h")]
+                                                               "radfoam_hip_sh_entries.h",
+                                                               "radfoam_hip_entry_weights.h")]
 OBJ_DIR = os.path.join(_CSRC, "_obj")
 OUTPUT = os.path.join(_HERE, "libradfoam_hip.so")
 

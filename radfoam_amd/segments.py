@@ -13,7 +13,8 @@ channels [S, C]), with kernels of its own for float32 tensors on the device (rf_
 ``ray_distortion`` is the regulariser that goes with it: Mip-NeRF 360's distortion loss of every ray from the same
 per-entry density, by the same scheme of kernels (rf_distortion.hip).  ``ray_quantiles`` is the depth
 output: where along the ray the transmittance of that density falls through given levels (rf_quantiles.hip, DESIGN
-4.14).
+4.14).  ``entry_weights`` gives the compositing weight and the transmittance of every entry themselves, for whatever is
+not a sum of them along the ray (rf_entry_weights.hip).
 """
 from __future__ import annotations
 
@@ -514,6 +515,125 @@ def ray_quantiles(seg, sigma: torch.Tensor, quantiles: torch.Tensor, backend=Non
             raise RuntimeError("seg['offsets'][-1] must be the number of entries")
         return _ray_quantiles_torch(seg["offsets"].to(sigma.device), seg["t_enter"], seg["t_exit"], sigma, levels)
     return _RayQuantiles.apply(sigma, seg["t_enter"], seg["t_exit"], levels, seg["offsets"])
+
+
+def _check_weights_inputs(seg, sigma):
+    if sigma.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("sigma must have float32 or float64 dtype")
+    if sigma.dim() != 1:
+        raise RuntimeError("expected sigma [S]")
+    offsets = _check_offsets(seg["offsets"])
+    total = sigma.size(0)
+    if seg["t_enter"].numel() != total or seg["t_exit"].numel() != total:
+        raise RuntimeError("sigma, seg['t_enter'] and seg['t_exit'] must have one element per entry")
+    return offsets.numel() - 1, total
+
+
+def _entry_weights_torch(offsets, t_enter, t_exit, sigma):
+    """The definition with the operations of ``_composite_entries_torch``, stopping before its ``index_add``: float64
+    throughout, the sum over a ray's earlier entries as a difference of one list-wide cumulative sum.  Autograd
+    differentiates it.  ``offsets`` is on the device of ``sigma``.  Returns (weights, transmittance)."""
+    dev, dtype = sigma.device, sigma.dtype
+    t_enter = t_enter.to(dev).to(torch.float64).reshape(-1)
+    t_exit = t_exit.to(dev).to(torch.float64).reshape(-1)
+    dt = torch.where(torch.isinf(t_exit), torch.zeros_like(t_exit), (t_exit - t_enter).clamp_min(0.0))
+    log_keep = -sigma.to(torch.float64) * dt                       # -x = log(1 - alpha) of every entry
+    log_before = _sums_in_ray(log_keep, offsets, _entry_rays(offsets, sigma.size(0)))[0]
+    transmittance = torch.exp(log_before)                          # exp(0) = 1 at every ray's first entry
+    return (transmittance * -torch.expm1(log_keep)).to(dtype), transmittance.to(dtype)
+
+
+class _EntryWeights(torch.autograd.Function):
+    """``entry_weights`` through the kernels of rf_entry_weights.hip: float32 CUDA tensors, each gradient only where its
+    input needs one, and an output nobody used costs neither a zero tensor nor a read.  Nothing but the inputs is kept
+    for the backward, which sweeps the list twice."""
+
+    @staticmethod
+    def forward(ctx, sigma, t_enter, t_exit, offsets, with_transmittance):
+        from . import _lib
+        from .pipeline import _ptr, _stream_ptr
+
+        dev = sigma.device
+        num_rays, total = offsets.numel() - 1, sigma.size(0)
+        if num_rays >= 2 ** 31:
+            raise RuntimeError("too many rays for the kernel")
+        offsets = offsets.to(dev).contiguous()
+        sigma_c = sigma.detach().contiguous()
+        t_enter_c, t_exit_c = _times_for_kernel(ctx, dev, t_enter, t_exit)
+        ctx.save_for_backward(sigma_c, t_enter_c, t_exit_c, offsets)
+        ctx.set_materialize_grads(False)
+        # entries outside offsets[0] .. offsets[R] are not written by the kernel: there are none in a sound list
+        new = torch.empty_like if num_rays > 0 and total > 0 else torch.zeros_like
+        weights = new(sigma_c)
+        transmittance = new(sigma_c) if with_transmittance else None
+        if num_rays > 0 and total > 0:
+            with torch.cuda.device(dev):
+                rc = _lib.load().rf_entry_weights_forward(
+                    num_rays, _ptr(offsets), total, _ptr(t_enter_c), _ptr(t_exit_c), _ptr(sigma_c), _ptr(weights),
+                    _ptr(transmittance), _stream_ptr(dev))
+            _lib.check(rc)
+        return (weights, transmittance) if with_transmittance else weights
+
+    @staticmethod
+    def backward(ctx, grad_weights, grad_transmittance=None):
+        from . import _lib
+        from .pipeline import _ptr, _stream_ptr
+
+        sigma, t_enter, t_exit, offsets = ctx.saved_tensors
+        dev = sigma.device
+        num_rays, total = offsets.numel() - 1, sigma.size(0)
+        want = ctx.needs_input_grad[:3]
+        runs = num_rays > 0 and total > 0 and any(want)
+        new = torch.empty_like if runs else torch.zeros_like
+        grads = [new(sigma) if w else None for w in want]
+        if runs:
+            g_w, g_t = (None if g is None else g.to(torch.float32).contiguous()
+                        for g in (grad_weights, grad_transmittance))             # None: zeros, and not read
+            with torch.cuda.device(dev):
+                rc = _lib.load().rf_entry_weights_backward(
+                    num_rays, _ptr(offsets), total, _ptr(t_enter), _ptr(t_exit), _ptr(sigma), _ptr(g_w), _ptr(g_t),
+                    _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _stream_ptr(dev))
+            _lib.check(rc)
+        return (grads[0], *_times_grads(ctx, grads[1], grads[2]), None, None)
+
+
+def entry_weights(seg, sigma: torch.Tensor, return_transmittance=False, backend=None):
+    """weights [S], or (weights [S], transmittance [S]) with ``return_transmittance``: the compositing weight of every
+    entry of ``seg`` (the dict ``Pipeline.trace_segments`` or ``trace_differentiable_segments`` returns; ``offsets``
+    int64 [R+1] and ``t_enter`` / ``t_exit`` [S] are read, ``cells`` is not) and the transmittance in front of it, for a
+    density ``sigma`` [S] PER ENTRY, float32 or float64.  Per ray, over its entries in order (the
+    definitions of ``composite_entries`` word for word):
+
+        dt = 0 where t_exit is infinite, else max(t_exit - t_enter, 0),      x = sigma dt
+        T = exp(-(sum of x over the ray's earlier entries))          transmittance
+        w = T (1 - exp(-x))                                          weights
+
+    ``composite_entries`` is the sum of ``w values`` per ray; this is for everything that is not linear in the weights:
+    the ray entropy ``-sum w log w`` (examples/weight_entropy.py), a proposal loss between two densities on one walk, a
+    per-entry visibility T, the largest weight a cell ever gets, weight times error per cell through
+    ``reduce_entries``.  T is exactly 1 at every ray's first entry and w is exactly 0 behind an infinite ``t_exit``.
+    The results have the dtype and device of ``sigma``.
+
+    Differentiable in ``sigma``, ``seg["t_enter"]`` and ``seg["t_exit"]`` (which carry the gradient on to the points and
+    the rays when they come from ``trace_differentiable_segments``).  The times' gradient follows torch's
+    ``clamp_min``: an entry with t_exit >= t_enter, both finite, passes it on, t_exit < t_enter does not, and an entry
+    with an infinite t_exit gets exact zeros in every gradient.
+
+    ``backend``: None, "hip" or "torch", as in ``composite_entries``.  None is "hip" for float32 CUDA ``sigma`` and
+    "torch" for everything else.  "hip" runs the kernels of rf_entry_weights.hip (one wave owns a run of consecutive
+    rays, a segmented scan in double, one rounding to float32, no atomics: the same bits from call to call, gradients
+    included; the times are read as float32; an output that the loss does not use is not read back in the backward).
+    "torch" restates the definition in float64 with one list-wide cumulative sum, differentiated by autograd, on any
+    device; no Python loop over rays.  ``offsets[-1] == S`` is checked on the torch path only, and there only when
+    ``seg["offsets"]`` lives on the CPU.  (The kernels clamp every offset to 0 .. S instead.)"""
+    _check_weights_inputs(seg, sigma)
+    if _choose_backend(backend, sigma, "sigma") == "torch":
+        if not seg["offsets"].is_cuda and int(seg["offsets"][-1]) != sigma.size(0):
+            raise RuntimeError("seg['offsets'][-1] must be the number of entries")
+        weights, transmittance = _entry_weights_torch(seg["offsets"].to(sigma.device), seg["t_enter"], seg["t_exit"],
+                                                      sigma)
+        return (weights, transmittance) if return_transmittance else weights
+    return _EntryWeights.apply(sigma, seg["t_enter"], seg["t_exit"], seg["offsets"], bool(return_transmittance))
 
 
 _NONE = 0xFFFFFFFF
