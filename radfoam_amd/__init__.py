@@ -8,7 +8,8 @@ include/radfoam_hip.h; everything else the reference module exports is a torch/s
 package ``radfoam/`` at the repo root.
 """
 from .cells import CellEntries, cell_entries, gather_cells, reduce_entries
-from .geometry import CellGeometry, cell_geometry, cell_geometry_grad, cell_surface, differentiable_cell_geometry
+from .geometry import (CellGeometry, cell_geometry, cell_geometry_grad, cell_surface, differentiable_cell_geometry,
+                       face_area_grad)
 from .pipeline import Pipeline, create_pipeline, invalidate_caches
 from .scene_ops import pack_attributes
 from .segments import (composite_entries, composite_segments, entry_weights, ray_distortion, ray_quantiles,
@@ -23,5 +24,5 @@ __all__ = [
     "invalidate_caches", "CellGeometry", "cell_geometry", "cell_surface", "composite_segments",
     "segment_points_grad", "segment_rays_grad", "composite_entries", "cell_geometry_grad",
     "differentiable_cell_geometry", "ray_distortion", "ray_quantiles", "CellEntries", "cell_entries",
-    "gather_cells", "reduce_entries", "sh_entries", "entry_weights",
+    "gather_cells", "reduce_entries", "sh_entries", "entry_weights", "face_area_grad",
 ]

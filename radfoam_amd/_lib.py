@@ -66,7 +66,7 @@ class LaunchOpts(C.Structure):
 
 # every symbol include/radfoam_hip.h, radfoam_hip_geometry.h, radfoam_hip_geometry_grad.h, radfoam_hip_segments.h,
 # radfoam_hip_composite.h, radfoam_hip_distortion.h, radfoam_hip_quantiles.h, radfoam_hip_cell_reduce.h,
-# radfoam_hip_sh_entries.h and radfoam_hip_entry_weights.h declare:
+# radfoam_hip_sh_entries.h, radfoam_hip_entry_weights.h and radfoam_hip_face_area_grad.h declare:
 # name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -151,6 +151,8 @@ SYMBOLS = {
     "rf_entry_weights_rays_per_wave": (_U32, []),
     "rf_entry_weights_forward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "rf_entry_weights_backward": (_INT, [_U32, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rf_face_area_grad_workspace_bytes": (C.c_size_t, [_U32, _U32]),
+    "rf_face_area_grad": (_INT, [_P, _U32, _P, _P, _U32, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

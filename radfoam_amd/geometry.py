@@ -4,11 +4,14 @@
   cell_surface    the faces between selected and unselected cells, as triangles: the foam's own watertight surface of
                   e.g. ``density > tau``
   cell_geometry_grad            the gradient of a function of the volumes and centroids with respect to ``points``
-  differentiable_cell_geometry  cell_geometry whose volume and centroid carry autograd to ``points``
+  face_area_grad                the gradient of a function of the face areas with respect to ``points``
+  differentiable_cell_geometry  cell_geometry whose volume and centroid (and, on request, face areas) carry autograd to
+                                ``points``
 
 Cell ``a`` is the intersection of the half-spaces of its row of ``point_adjacency`` (taken as given); no tetrahedra are
-involved.  All take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip and csrc/rf_cell_geometry_grad.hip
-behind the C-ABI of include/radfoam_hip_geometry.h and include/radfoam_hip_geometry_grad.h; there is no CPU path.
+involved.  All take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip, csrc/rf_cell_geometry_grad.hip
+and csrc/rf_face_area_grad.hip behind the C-ABI of include/radfoam_hip_geometry.h, include/radfoam_hip_geometry_grad.h
+and include/radfoam_hip_face_area_grad.h; there is no CPU path.
 """
 from __future__ import annotations
 
@@ -182,30 +185,87 @@ def cell_geometry_grad(points: torch.Tensor, point_adjacency: torch.Tensor, poin
                               _upstream("grad_centroid", grad_centroid, (n, 3), dev))
 
 
+def _run_face_area_grad(p, adj, off, bbox, face_area, grad_face_area):
+    """grad_points f64[N,3]; one synchronisation, to read whether a row was refused."""
+    n, e, dev = p.size(0), adj.numel(), p.device
+    lib = _lib.load()
+    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rf_face_area_grad_workspace_bytes(n, e)), 256), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.rf_face_area_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(face_area),
+                                   _ptr(grad_face_area), _ptr(grad), _ptr(status), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc)
+    if n:
+        worst, cell = status.max(0)
+        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
+        if worst:
+            raise RuntimeError(f"face_area_grad: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    return grad
+
+
+def face_area_grad(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
+                   geometry: CellGeometry, grad_face_area: torch.Tensor) -> torch.Tensor:
+    """f64[N,3]: the gradient with respect to ``points`` of  L = sum_s grad_face_area[s] face_area[s]  over the adjacency
+    slots whose area is finite, ``geometry`` being what cell_geometry returned for the same arguments.
+
+    Face {a,b} weighs G_ab = g[a->b] + g[b->a] (each where that slot's area is finite; what arrives for a slot of area
+    +inf, NaN and inf included, is ignored, and so is a slot of area exactly 0, which the forward clipped away).  A
+    flat face changes its area through the in-plane motion of its edges, and every finite Voronoi edge of cell a, dual to
+    a Delaunay triangle (a,b,c), adds  l (lambda_b + lambda_c) (y - p_a)  to grad p_a, l and y the edge's length and
+    midpoint and lambda from G_ab, G_ac, G_bc and the triangle ("Point gradients of the face areas").  A
+    gather over each site's own row with one look-up in a neighbour's, bit-reproducible: the exact gradient for a
+    symmetric adjacency such as a Delaunay CSR; where a mate slot or the slot b->c does not exist its weight is 0.
+    ``grad_face_area`` is a floating-point [E] CUDA tensor.  Raises RuntimeError naming the cell like cell_geometry."""
+    p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+    e, dev = adj.numel(), p.device
+    face_area = getattr(geometry, "face_area", None)
+    if (not isinstance(face_area, torch.Tensor) or not face_area.is_cuda or face_area.device != dev
+            or face_area.dtype != torch.float64 or face_area.shape != (e,)):
+        raise RuntimeError("geometry must be the CellGeometry cell_geometry returned for these points")
+    if grad_face_area is None:
+        raise RuntimeError(f"grad_face_area must be a floating-point CUDA tensor of shape {[e]} on the device of points")
+    return _run_face_area_grad(p, adj, off, bbox, face_area.detach().contiguous(),
+                               _upstream("grad_face_area", grad_face_area, (e,), dev))
+
+
 class _DifferentiableCellGeometry(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, points, point_adjacency, point_adjacency_offsets):
+    def forward(ctx, points, point_adjacency, point_adjacency_offsets, with_face_area):
         p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
         geo = _run_geometry(p, adj, off, bbox)[0]
-        ctx.save_for_backward(p, adj, off, bbox, geo.volume, geo.centroid, geo.bounded)
+        ctx.save_for_backward(p, adj, off, bbox, geo.volume, geo.centroid, geo.bounded, geo.face_area)
         ctx.points_dtype = points.dtype
-        ctx.mark_non_differentiable(geo.bounded, geo.face_area)
+        ctx.set_materialize_grads(False)      # an output the loss leaves out arrives as None and its operator is not run
+        if with_face_area:
+            ctx.mark_non_differentiable(geo.bounded)
+        else:
+            ctx.mark_non_differentiable(geo.bounded, geo.face_area)
         return geo.volume, geo.centroid, geo.bounded, geo.face_area
 
     @staticmethod
-    def backward(ctx, grad_volume, grad_centroid, _grad_bounded, _grad_face_area):
-        p, adj, off, bbox, volume, centroid, bounded = ctx.saved_tensors
-        n, dev = p.size(0), p.device
-        grad = _run_geometry_grad(p, adj, off, bbox, volume, centroid, bounded.view(torch.uint8),
-                                  _upstream("grad_volume", grad_volume, (n,), dev),
-                                  _upstream("grad_centroid", grad_centroid, (n, 3), dev))
-        return grad.to(ctx.points_dtype), None, None
+    def backward(ctx, grad_volume, grad_centroid, _grad_bounded, grad_face_area):
+        p, adj, off, bbox, volume, centroid, bounded, face_area = ctx.saved_tensors
+        n, e, dev = p.size(0), adj.numel(), p.device
+        grad = None
+        if grad_volume is not None or grad_centroid is not None:
+            grad = _run_geometry_grad(p, adj, off, bbox, volume, centroid, bounded.view(torch.uint8),
+                                      _upstream("grad_volume", grad_volume, (n,), dev),
+                                      _upstream("grad_centroid", grad_centroid, (n, 3), dev))
+        if grad_face_area is not None:
+            part = _run_face_area_grad(p, adj, off, bbox, face_area, _upstream("grad_face_area", grad_face_area, (e,), dev))
+            grad = part if grad is None else grad + part
+        if grad is None:
+            grad = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        return grad.to(ctx.points_dtype), None, None, None
 
 
 def differentiable_cell_geometry(points: torch.Tensor, point_adjacency: torch.Tensor,
-                                 point_adjacency_offsets: torch.Tensor) -> CellGeometry:
+                                 point_adjacency_offsets: torch.Tensor, face_area: bool = False) -> CellGeometry:
     """cell_geometry, bit for bit, with ``volume`` and ``centroid`` carrying autograd to ``points`` (cell_geometry_grad:
-    summed in double, returned in the dtype of ``points``).  ``bounded`` and ``face_area`` are not differentiable.  Mask
-    the unbounded cells out of a loss (their volume is +inf and their centroid NaN); what flows back for them is
-    ignored."""
-    return CellGeometry(*_DifferentiableCellGeometry.apply(points, point_adjacency, point_adjacency_offsets))
+    summed in double, returned in the dtype of ``points``).  With ``face_area=True`` the face areas carry autograd as well
+    (face_area_grad); the backward runs each operator only where something arrived and adds the two in double.  By
+    default ``bounded`` and ``face_area`` are not differentiable.  Mask the unbounded cells and faces out of a loss (their
+    volume and area are +inf and their centroid NaN); what flows back for them is ignored."""
+    return CellGeometry(*_DifferentiableCellGeometry.apply(points, point_adjacency, point_adjacency_offsets,
+                                                           bool(face_area)))
