@@ -10,6 +10,7 @@ package ``radfoam/`` at the repo root.
 from .cells import CellEntries, cell_entries, gather_cells, reduce_entries
 from .geometry import (CellGeometry, cell_geometry, cell_geometry_grad, cell_surface, differentiable_cell_geometry,
                        face_area_grad)
+from .mesh import CellMesh, cell_mesh, mesh_vertices, mesh_vertices_grad
 from .pipeline import Pipeline, create_pipeline, invalidate_caches
 from .scene_ops import pack_attributes
 from .segments import (composite_entries, composite_segments, entry_weights, ray_distortion, ray_quantiles,
@@ -24,5 +25,6 @@ __all__ = [
     "invalidate_caches", "CellGeometry", "cell_geometry", "cell_surface", "composite_segments",
     "segment_points_grad", "segment_rays_grad", "composite_entries", "cell_geometry_grad",
     "differentiable_cell_geometry", "ray_distortion", "ray_quantiles", "CellEntries", "cell_entries",
-    "gather_cells", "reduce_entries", "sh_entries", "entry_weights", "face_area_grad",
+    "gather_cells", "reduce_entries", "sh_entries", "entry_weights", "face_area_grad", "CellMesh", "cell_mesh",
+    "mesh_vertices", "mesh_vertices_grad",
 ]
