@@ -7,11 +7,13 @@
   face_area_grad                the gradient of a function of the face areas with respect to ``points``
   differentiable_cell_geometry  cell_geometry whose volume and centroid (and, on request, face areas) carry autograd to
                                 ``points``
+  cell_moments    the second moment of every cell about its site and about its centroid: the cell's shape
 
 Cell ``a`` is the intersection of the half-spaces of its row of ``point_adjacency`` (taken as given); no tetrahedra are
-involved.  All take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip, csrc/rf_cell_geometry_grad.hip
-and csrc/rf_face_area_grad.hip behind the C-ABI of include/radfoam_hip_geometry.h, include/radfoam_hip_geometry_grad.h
-and include/radfoam_hip_face_area_grad.h; there is no CPU path.
+involved.  All take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip, csrc/rf_cell_geometry_grad.hip,
+csrc/rf_face_area_grad.hip and csrc/rf_cell_moments.hip behind the C-ABI of include/radfoam_hip_geometry.h,
+include/radfoam_hip_geometry_grad.h, include/radfoam_hip_face_area_grad.h and include/radfoam_hip_moments.h; there is no
+CPU path.
 """
 from __future__ import annotations
 
@@ -32,6 +34,12 @@ class CellGeometry(NamedTuple):
     centroid: torch.Tensor    # f64[N,3]; NaN for an unbounded cell
     bounded: torch.Tensor     # bool[N]
     face_area: torch.Tensor   # f64[E], aligned with point_adjacency; +inf for an unbounded face
+
+
+class CellMoments(NamedTuple):
+    site_moment: torch.Tensor      # f64[N,6]: int (x - p)(x - p)^T dx as xx, yy, zz, xy, xz, yz; NaN for an unbounded cell
+    central_moment: torch.Tensor   # f64[N,6]: the same about the centroid; NaN for an unbounded cell
+    geometry: CellGeometry         # the volumes and centroids the central moment was formed with
 
 
 def _index_tensor(name, t, device):
@@ -98,6 +106,46 @@ def cell_geometry(points: torch.Tensor, point_adjacency: torch.Tensor,
     keep their finite areas.  Index tensors may be uint32, int32 or int64.  Raises RuntimeError naming the cell if a
     face needs more than 256 vertices or a row is malformed."""
     return _run_geometry(*_prepare(points, point_adjacency, point_adjacency_offsets))[0]
+
+
+def cell_moments(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
+                 geometry: CellGeometry | None = None) -> CellMoments:
+    """The second moments of every Voronoi cell, in double and relative to the site: ``site_moment`` f64[N,6] is
+    int_{cell a} y y^T dy with y = x - p_a, stored as xx, yy, zz, xy, xz, yz, and ``central_moment`` f64[N,6] is
+    site_moment - V_a m m^T with m = centroid[a] - p_a, the moment about the centroid.
+
+    The trace of ``site_moment`` is the cell's centroidal-Voronoi energy int |x - p_a|^2 dx, and ``central_moment /
+    volume`` the covariance of the uniform distribution on the cell: with the centroid as its mean, the cell's Gaussian.
+    An unbounded cell gets NaN in all twelve.  ``geometry`` is what cell_geometry returned for the same arguments; when
+    it is None cell_geometry runs first, and either way it comes back as the third field.  A gather over each site's own
+    row, bit-reproducible; not differentiable.  Raises RuntimeError naming the cell like cell_geometry."""
+    p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+    n, e, dev = p.size(0), adj.numel(), p.device
+    if geometry is None:
+        geometry = _run_geometry(p, adj, off, bbox)[0]
+    volume, centroid, bounded = (getattr(geometry, k, None) for k in ("volume", "centroid", "bounded"))
+    if (not all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev for t in (volume, centroid, bounded))
+            or volume.dtype != torch.float64 or volume.shape != (n,) or centroid.dtype != torch.float64
+            or centroid.shape != (n, 3) or bounded.dtype != torch.bool or bounded.shape != (n,)):
+        raise RuntimeError("geometry must be the CellGeometry cell_geometry returned for these points")
+    lib = _lib.load()
+    site = torch.empty((n, 6), dtype=torch.float64, device=dev)
+    central = torch.empty((n, 6), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rf_cell_moments_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
+    volume, centroid = volume.detach().contiguous(), centroid.detach().contiguous()
+    flags = bounded.contiguous().view(torch.uint8)
+    with torch.cuda.device(dev):
+        rc = lib.rf_cell_moments(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(volume), _ptr(centroid),
+                                 _ptr(flags), _ptr(site), _ptr(central), _ptr(status), _ptr(ws), ws.numel(),
+                                 _stream(dev))
+    _lib.check(rc)
+    if n:
+        worst, cell = status.max(0)
+        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
+        if worst:
+            raise RuntimeError(f"cell_moments: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    return CellMoments(site, central, geometry)
 
 
 def cell_surface(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
