@@ -8,12 +8,14 @@
   differentiable_cell_geometry  cell_geometry whose volume and centroid (and, on request, face areas) carry autograd to
                                 ``points``
   cell_moments    the second moment of every cell about its site and about its centroid: the cell's shape
+  cell_moments_grad             the gradient of a function of the second moments with respect to ``points``
+  differentiable_cell_moments   cell_moments whose moments, volume and centroid carry autograd to ``points``
 
 Cell ``a`` is the intersection of the half-spaces of its row of ``point_adjacency`` (taken as given); no tetrahedra are
 involved.  All take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip, csrc/rf_cell_geometry_grad.hip,
-csrc/rf_face_area_grad.hip and csrc/rf_cell_moments.hip behind the C-ABI of include/radfoam_hip_geometry.h,
-include/radfoam_hip_geometry_grad.h, include/radfoam_hip_face_area_grad.h and include/radfoam_hip_moments.h; there is no
-CPU path.
+csrc/rf_face_area_grad.hip, csrc/rf_cell_moments.hip and csrc/rf_cell_moments_grad.hip behind the C-ABI of
+include/radfoam_hip_geometry.h, include/radfoam_hip_geometry_grad.h, include/radfoam_hip_face_area_grad.h,
+include/radfoam_hip_moments.h and include/radfoam_hip_moments_grad.h; there is no CPU path.
 """
 from __future__ import annotations
 
@@ -118,9 +120,10 @@ def cell_moments(points: torch.Tensor, point_adjacency: torch.Tensor, point_adja
     volume`` the covariance of the uniform distribution on the cell: with the centroid as its mean, the cell's Gaussian.
     An unbounded cell gets NaN in all twelve.  ``geometry`` is what cell_geometry returned for the same arguments; when
     it is None cell_geometry runs first, and either way it comes back as the third field.  A gather over each site's own
-    row, bit-reproducible; not differentiable.  Raises RuntimeError naming the cell like cell_geometry."""
+    row, bit-reproducible; not differentiable (differentiable_cell_moments is, and cell_moments_grad is its operator).
+    Raises RuntimeError naming the cell like cell_geometry."""
     p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
-    n, e, dev = p.size(0), adj.numel(), p.device
+    n, dev = p.size(0), p.device
     if geometry is None:
         geometry = _run_geometry(p, adj, off, bbox)[0]
     volume, centroid, bounded = (getattr(geometry, k, None) for k in ("volume", "centroid", "bounded"))
@@ -128,23 +131,8 @@ def cell_moments(points: torch.Tensor, point_adjacency: torch.Tensor, point_adja
             or volume.dtype != torch.float64 or volume.shape != (n,) or centroid.dtype != torch.float64
             or centroid.shape != (n, 3) or bounded.dtype != torch.bool or bounded.shape != (n,)):
         raise RuntimeError("geometry must be the CellGeometry cell_geometry returned for these points")
-    lib = _lib.load()
-    site = torch.empty((n, 6), dtype=torch.float64, device=dev)
-    central = torch.empty((n, 6), dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(int(lib.rf_cell_moments_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
-    volume, centroid = volume.detach().contiguous(), centroid.detach().contiguous()
-    flags = bounded.contiguous().view(torch.uint8)
-    with torch.cuda.device(dev):
-        rc = lib.rf_cell_moments(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(volume), _ptr(centroid),
-                                 _ptr(flags), _ptr(site), _ptr(central), _ptr(status), _ptr(ws), ws.numel(),
-                                 _stream(dev))
-    _lib.check(rc)
-    if n:
-        worst, cell = status.max(0)
-        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
-        if worst:
-            raise RuntimeError(f"cell_moments: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    site, central = _run_moments(p, adj, off, bbox, volume.detach().contiguous(), centroid.detach().contiguous(),
+                                 bounded.contiguous().view(torch.uint8))
     return CellMoments(site, central, geometry)
 
 
@@ -306,6 +294,120 @@ class _DifferentiableCellGeometry(torch.autograd.Function):
         if grad is None:
             grad = torch.zeros((n, 3), dtype=torch.float64, device=dev)
         return grad.to(ctx.points_dtype), None, None, None
+
+
+def _run_moments(p, adj, off, bbox, volume, centroid, flags):
+    """(site f64[N,6], central f64[N,6]); one synchronisation, to read whether a cell was refused."""
+    n, e, dev = p.size(0), adj.numel(), p.device
+    lib = _lib.load()
+    site = torch.empty((n, 6), dtype=torch.float64, device=dev)
+    central = torch.empty((n, 6), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rf_cell_moments_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.rf_cell_moments(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(volume), _ptr(centroid),
+                                 _ptr(flags), _ptr(site), _ptr(central), _ptr(status), _ptr(ws), ws.numel(),
+                                 _stream(dev))
+    _lib.check(rc)
+    if n:
+        worst, cell = status.max(0)
+        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
+        if worst:
+            raise RuntimeError(f"cell_moments: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    return site, central
+
+
+def _run_moments_grad(p, adj, off, bbox, volume, centroid, bounded, grad_site_moment, grad_central_moment):
+    """grad_points f64[N,3]; one synchronisation, to read whether a row was refused."""
+    n, e, dev = p.size(0), adj.numel(), p.device
+    lib = _lib.load()
+    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rf_cell_moments_grad_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
+    opt = lambda t: None if t is None else _ptr(t)
+    with torch.cuda.device(dev):
+        rc = lib.rf_cell_moments_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(volume), _ptr(centroid),
+                                      _ptr(bounded), opt(grad_site_moment), opt(grad_central_moment), _ptr(grad),
+                                      _ptr(status), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc)
+    if n:
+        worst, cell = status.max(0)
+        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
+        if worst:
+            raise RuntimeError(f"cell_moments_grad: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    return grad
+
+
+def cell_moments_grad(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
+                      geometry: CellGeometry, grad_site_moment=None, grad_central_moment=None) -> torch.Tensor:
+    """f64[N,3]: the gradient with respect to ``points`` of  L = sum_a <grad_site_moment[a], site_moment[a]> +
+    <grad_central_moment[a], central_moment[a]>  over the bounded cells, each bracket the plain sum over the six stored
+    numbers (xx, yy, zz, xy, xz, yz), ``geometry`` being what cell_geometry returned for the same arguments.
+
+    With G_a and H_a the symmetric matrices of the two upstreams (the diagonal as it is, half of each off-diagonal number
+    on both sides) and Psi_a(x) = (x - p_a)^T G_a (x - p_a) + (x - c_a)^T H_a (x - c_a), Psi_a = 0 for an unbounded cell
+    (whatever arrives for it, NaN and inf included, is ignored),
+    grad p_a = sum over b in a's row of (1 / |p_b - p_a|) int_{F_ab} (Psi_a - Psi_b)(x) (x - p_a) dA  -  2 V_a G_a
+    (c_a - p_a); the central moment has no direct term, because the first moment about the centroid vanishes.  Either
+    upstream (f64 or f32, [N,6]) may be None.  A gather over each site's own row, bit-reproducible: the exact gradient
+    for a symmetric adjacency such as a Delaunay CSR; where a row omits a site that lists it, the omitted terms are
+    dropped.  Raises RuntimeError naming the cell like cell_geometry."""
+    p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+    n, dev = p.size(0), p.device
+    volume, centroid, bounded = (getattr(geometry, k, None) for k in ("volume", "centroid", "bounded"))
+    if (not all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev for t in (volume, centroid, bounded))
+            or volume.dtype != torch.float64 or volume.shape != (n,) or centroid.dtype != torch.float64
+            or centroid.shape != (n, 3) or bounded.dtype != torch.bool or bounded.shape != (n,)):
+        raise RuntimeError("geometry must be the CellGeometry cell_geometry returned for these points")
+    return _run_moments_grad(p, adj, off, bbox, volume.detach().contiguous(), centroid.detach().contiguous(),
+                             bounded.contiguous().view(torch.uint8),
+                             _upstream("grad_site_moment", grad_site_moment, (n, 6), dev),
+                             _upstream("grad_central_moment", grad_central_moment, (n, 6), dev))
+
+
+class _DifferentiableCellMoments(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, point_adjacency, point_adjacency_offsets):
+        p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+        geo = _run_geometry(p, adj, off, bbox)[0]
+        site, central = _run_moments(p, adj, off, bbox, geo.volume, geo.centroid, geo.bounded.view(torch.uint8))
+        ctx.save_for_backward(p, adj, off, bbox, geo.volume, geo.centroid, geo.bounded)
+        ctx.points_dtype = points.dtype
+        ctx.set_materialize_grads(False)      # an output the loss leaves out arrives as None and its operator is not run
+        ctx.mark_non_differentiable(geo.bounded, geo.face_area)
+        return site, central, geo.volume, geo.centroid, geo.bounded, geo.face_area
+
+    @staticmethod
+    def backward(ctx, grad_site, grad_central, grad_volume, grad_centroid, _grad_bounded, _grad_face_area):
+        p, adj, off, bbox, volume, centroid, bounded = ctx.saved_tensors
+        n, dev = p.size(0), p.device
+        flags = bounded.view(torch.uint8)
+        grad = None
+        if grad_site is not None or grad_central is not None:
+            grad = _run_moments_grad(p, adj, off, bbox, volume, centroid, flags,
+                                     _upstream("grad_site_moment", grad_site, (n, 6), dev),
+                                     _upstream("grad_central_moment", grad_central, (n, 6), dev))
+        if grad_volume is not None or grad_centroid is not None:
+            part = _run_geometry_grad(p, adj, off, bbox, volume, centroid, flags,
+                                      _upstream("grad_volume", grad_volume, (n,), dev),
+                                      _upstream("grad_centroid", grad_centroid, (n, 3), dev))
+            grad = part if grad is None else grad + part
+        if grad is None:
+            grad = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        return grad.to(ctx.points_dtype), None, None
+
+
+def differentiable_cell_moments(points: torch.Tensor, point_adjacency: torch.Tensor,
+                                point_adjacency_offsets: torch.Tensor) -> CellMoments:
+    """cell_moments, bit for bit, with ``site_moment`` and ``central_moment`` carrying autograd to ``points``
+    (cell_moments_grad), and ``geometry.volume`` and ``geometry.centroid`` as in differentiable_cell_geometry
+    (cell_geometry_grad): ``central_moment / volume[:, None]``, the covariance, and the trace of ``site_moment``, the
+    centroidal-Voronoi energy, are differentiable end to end.  The backward runs each operator only where something
+    arrived and adds the two in double; the result is returned in the dtype of ``points``.  ``geometry.bounded`` and
+    ``geometry.face_area`` are not differentiable.  Mask the unbounded cells out of a loss (their moments and centroid
+    are NaN and their volume +inf); what flows back for them is ignored."""
+    site, central, *geo = _DifferentiableCellMoments.apply(points, point_adjacency, point_adjacency_offsets)
+    return CellMoments(site, central, CellGeometry(*geo))
 
 
 def differentiable_cell_geometry(points: torch.Tensor, point_adjacency: torch.Tensor,
