@@ -7,18 +7,21 @@
   face_area_grad                the gradient of a function of the face areas with respect to ``points``
   differentiable_cell_geometry  cell_geometry whose volume and centroid (and, on request, face areas) carry autograd to
                                 ``points``
+  cell_geometry_in_box          cell_geometry of the cells clipped to an axis-aligned box: every cell bounded, plus the
+                                area each cell takes of each wall
   cell_moments    the second moment of every cell about its site and about its centroid: the cell's shape
   cell_moments_grad             the gradient of a function of the second moments with respect to ``points``
   differentiable_cell_moments   cell_moments whose moments, volume and centroid carry autograd to ``points``
 
 Cell ``a`` is the intersection of the half-spaces of its row of ``point_adjacency`` (taken as given); no tetrahedra are
 involved.  All take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip, csrc/rf_cell_geometry_grad.hip,
-csrc/rf_face_area_grad.hip, csrc/rf_cell_moments.hip and csrc/rf_cell_moments_grad.hip behind the C-ABI of
-include/radfoam_hip_geometry.h, include/radfoam_hip_geometry_grad.h, include/radfoam_hip_face_area_grad.h,
-include/radfoam_hip_moments.h and include/radfoam_hip_moments_grad.h; there is no CPU path.
+csrc/rf_face_area_grad.hip, csrc/rf_cell_moments.hip, csrc/rf_cell_moments_grad.hip and csrc/rf_cell_box.hip behind the
+C-ABI of include/radfoam_hip_geometry.h, include/radfoam_hip_geometry_grad.h, include/radfoam_hip_face_area_grad.h,
+include/radfoam_hip_moments.h, include/radfoam_hip_moments_grad.h and include/radfoam_hip_box.h; there is no CPU path.
 """
 from __future__ import annotations
 
+import math
 from typing import NamedTuple
 
 import torch
@@ -36,6 +39,14 @@ class CellGeometry(NamedTuple):
     centroid: torch.Tensor    # f64[N,3]; NaN for an unbounded cell
     bounded: torch.Tensor     # bool[N]
     face_area: torch.Tensor   # f64[E], aligned with point_adjacency; +inf for an unbounded face
+
+
+class BoxedCellGeometry(NamedTuple):
+    volume: torch.Tensor      # f64[N]; finite, >= 0 up to rounding
+    centroid: torch.Tensor    # f64[N,3]; NaN for an empty cell
+    nonempty: torch.Tensor    # bool[N]: volume > 0
+    face_area: torch.Tensor   # f64[E], aligned with point_adjacency: the part of the face inside the box; finite
+    wall_area: torch.Tensor   # f64[N,6]: the part of each wall that bounds the cell, walls x-, x+, y-, y+, z-, z+
 
 
 class CellMoments(NamedTuple):
@@ -108,6 +119,70 @@ def cell_geometry(points: torch.Tensor, point_adjacency: torch.Tensor,
     keep their finite areas.  Index tensors may be uint32, int32 or int64.  Raises RuntimeError naming the cell if a
     face needs more than 256 vertices or a row is malformed."""
     return _run_geometry(*_prepare(points, point_adjacency, point_adjacency_offsets))[0]
+
+
+def _box_six(box):
+    """``box`` as six Python floats (lo, hi): a sequence or tensor of six numbers, or a [2,3] tensor; ValueError unless
+    they are finite with lo < hi in every axis."""
+    try:
+        flat = box.detach().reshape(-1).tolist() if isinstance(box, torch.Tensor) else [x for x in box]
+        if len(flat) == 2 and not isinstance(box, torch.Tensor):       # ((lo), (hi))
+            flat = [x for part in flat for x in part]
+        six = [float(x) for x in flat]
+    except (TypeError, ValueError) as exc:
+        raise ValueError("box must be six numbers (lo[3], hi[3])") from exc
+    if len(six) != 6:
+        raise ValueError(f"box must be six numbers (lo[3], hi[3]), not {len(six)}")
+    if not all(math.isfinite(x) for x in six) or not all(math.isfinite(six[k + 3] - six[k]) for k in range(3)):
+        raise ValueError("box must be finite")
+    if not all(six[k] < six[k + 3] for k in range(3)):
+        raise ValueError("box must have lo < hi in every axis")
+    return six
+
+
+def _run_geometry_in_box(p, adj, off, bbox, six):
+    """(BoxedCellGeometry, face_vertices int32[E], wall_vertices int32[N,6]); one synchronisation, to read whether a cell
+    was refused."""
+    n, e, dev = p.size(0), adj.numel(), p.device
+    lib = _lib.load()
+    volume = torch.empty(n, dtype=torch.float64, device=dev)
+    centroid = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    nonempty = torch.empty(n, dtype=torch.uint8, device=dev)
+    face_area = torch.empty(e, dtype=torch.float64, device=dev)
+    face_vertices = torch.empty(e, dtype=torch.int32, device=dev)
+    wall_area = torch.empty((n, 6), dtype=torch.float64, device=dev)
+    wall_vertices = torch.empty((n, 6), dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rf_cell_box_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.rf_cell_box(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), *six, _ptr(volume), _ptr(centroid),
+                             _ptr(nonempty), _ptr(face_area), _ptr(face_vertices), _ptr(wall_area), _ptr(wall_vertices),
+                             _ptr(status), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc)
+    if n:
+        worst, cell = status.max(0)
+        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
+        if worst:
+            raise RuntimeError(f"cell_geometry_in_box: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    return BoxedCellGeometry(volume, centroid, nonempty.bool(), face_area, wall_area), face_vertices, wall_vertices
+
+
+def cell_geometry_in_box(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
+                         box) -> BoxedCellGeometry:
+    """Every Voronoi cell clipped to the axis-aligned ``box``: volume f64[N], centroid f64[N,3], nonempty bool[N],
+    face_area f64[E] (the part of face (a,b) inside the box, aligned with ``point_adjacency``) and wall_area f64[N,6]
+    (the part of each wall that bounds the cell; wall 2k is x_k >= lo_k, wall 2k+1 is x_k <= hi_k), in double.
+
+    ``box`` is six numbers (lo, hi) as a sequence or tensor, or a [2,3] tensor; it is read on the host as doubles and
+    need not contain the points.  Cell a is the intersection of the half-spaces of its row and of the six walls, so every
+    cell is a bounded polytope and the cells of a Delaunay CSR partition the box: sum volume = the box's volume, and
+    nothing is +inf.  A site outside the box still owns what its cell cuts out of the box.  An empty cell has volume 0,
+    centroid NaN, areas 0 and nonempty False (nonempty is volume > 0; a flat cell may fall on either side by rounding);
+    a cell with an empty row is the whole box.  Where a wall coincides with a bisector plane the row's face keeps the area
+    and the wall gets 0.  Bit-reproducible; not differentiable.  Raises ValueError for a box that is not finite with
+    lo < hi, and RuntimeError naming the cell like cell_geometry."""
+    six = _box_six(box)
+    return _run_geometry_in_box(*_prepare(points, point_adjacency, point_adjacency_offsets), six)[0]
 
 
 def cell_moments(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
