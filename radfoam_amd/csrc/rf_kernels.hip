@@ -1805,6 +1805,31 @@ __global__ __launch_bounds__(kBlock) void backward_replay_kernel(BwdParams p) {
 #ifndef RF_ROWS_FROM_BASIS
 #define RF_ROWS_FROM_BASIS 1
 #endif
+// The epoch flush (cache_flush and the two barriers around it):
+//   RF_FLUSH_NARROW: a byte per row says whether the row ever received colour or point gradients since it was
+//     taken.  A row that did not ("narrow": one double out of NCOL can be non-zero, most rows of a frame whose rays
+//     cross cells of density 0) is flushed by its owning thread alone, all such rows of a wave in one pass; only
+//     the wide rows go through the cooperative loop.
+// Measured on the benchmark frame (profiles/r07/b_image_backward_flush_ab.log): backward 3.75 -> 3.60 ms.  A block
+// evicts 17 rows per epoch, 13 of them narrow.
+// Measured out in the same log, each on top of the narrow pass:
+//   * the block's "is any lane alive" through a flag word in LDS between the epoch's own two barriers instead of
+//     __syncthreads_or (which brings two barriers of its own): 0.01-0.07 ms better in each of six alternating pairs of
+//     runs, but less than the runs of one build differ among themselves -- the waves wait at the epoch's first
+//     barrier for the slowest of them (12 % of the wave clocks), not for the barrier instructions;
+//   * rows dealt to the waves (wave w, lane l owns row 4 l + w, so that the four waves evict equal shares instead of
+//     waves 0 and 1 owning most rows) and the evicted row's key by v_readlane instead of __shfl in the cooperative
+//     loop: nothing either way.  With 4 wide rows per block-epoch the loop is one or two trips and the closing barrier
+//     is 1-2 % of the wave clocks.
+#ifndef RF_FLUSH_NARROW
+#define RF_FLUSH_NARROW 1
+#endif
+// the sections build counts narrow and wide evictions whatever the flush does with the marks
+#if RF_FLUSH_NARROW || defined(RF_EXPERIMENT_SECTIONS)
+#define RF_WIDE_MARKS 1
+#else
+#define RF_WIDE_MARKS 0
+#endif
 constexpr int kCacheProbes = RF_CACHE_PROBES;
 constexpr uint32_t kEpoch = RF_CACHE_EPOCH;
 
@@ -1850,19 +1875,63 @@ __device__ __forceinline__ int cache_find(uint32_t *keys, uint32_t key) {
     return -1;
 }
 
+#ifdef RF_EXPERIMENT_SECTIONS
+// what the epochs of one wave did (sections build): wave clocks and rows
+struct FlushRecord {
+    unsigned long long arrive = 0, body = 0, close = 0;   // until the first barrier releases / the flush / the closing barrier
+    unsigned long long epochs = 0, wide = 0, narrow = 0, bypass = 0;   // rows evicted by this wave; lane adds that found no row
+};
+#endif
+
+// Between the two barriers of an epoch: every row has one owning thread, which alone decides whether the row stays
+// (touched during the epoch) or goes.  The owner of an evicted narrow row sends its one sum itself; the wide rows
+// evicted by a wave are then written by the whole wave, two rows per trip, 32 lanes per row.
 template <int NB>
-__device__ __forceinline__ void cache_flush(double *rows, uint32_t *keys, uint8_t *touch, bool all,
-                                              float *attr_grad, float *points_grad, uint32_t pitch) {
+__device__ __forceinline__ void cache_flush(double *rows, uint32_t *keys, uint8_t *touch, uint8_t *wide, bool all,
+                                              float *attr_grad, float *points_grad, uint32_t pitch
+#ifdef RF_EXPERIMENT_SECTIONS
+                                              , FlushRecord &rec
+#endif
+) {
     using L = CacheLayout<NB>;
     constexpr int A = 1 + 3 * NB;
     const uint32_t lane = threadIdx.x & 63u, col0 = threadIdx.x & 31u, base = threadIdx.x & ~63u;
     const bool mine_exists = threadIdx.x < (uint32_t)L::ROWS;
-    const uint32_t my_key = mine_exists ? keys[threadIdx.x] : kNone;
+    const uint32_t my_row = threadIdx.x;   // thread t owns row t
+    const uint32_t my_key = mine_exists ? keys[my_row] : kNone;
     const bool occupied = my_key != kNone;
-    const bool evict = occupied && (all || touch[threadIdx.x] == (uint8_t)0);
-    if (occupied && !evict) touch[threadIdx.x] = (uint8_t)0;
-    if (evict) keys[threadIdx.x] = kNone;
+    const bool evict = occupied && (all || touch[my_row] == (uint8_t)0);
+    if (occupied && !evict) touch[my_row] = (uint8_t)0;
+#if RF_WIDE_MARKS
+    bool is_wide = false;
+#endif
+    if (evict) {
+        keys[my_row] = kNone;
+#if RF_WIDE_MARKS
+        // a row keeps its mark from the first colour or point-gradient add until it is evicted
+        is_wide = wide[my_row] != (uint8_t)0;
+        if (is_wide) wide[my_row] = (uint8_t)0;
+#endif
+#if RF_FLUSH_NARROW
+        if (!is_wide) {
+            double *cell = rows + my_row * L::STRIDE + L::COL_DS;
+            const float v = (float)*cell;
+            if (v != 0.0f) {
+                *cell = 0.0;
+                grad_add(attr_grad + (size_t)my_key * pitch + (A - 1), v);
+            }
+        }
+#endif
+    }
+#ifdef RF_EXPERIMENT_SECTIONS
+    rec.wide += (unsigned long long)__builtin_popcountll(ballot(is_wide));
+    rec.narrow += (unsigned long long)__builtin_popcountll(ballot(evict && !is_wide));
+#endif
+#if RF_FLUSH_NARROW
+    unsigned long long todo = ballot(is_wide);
+#else
     unsigned long long todo = ballot(evict);
+#endif
     while (todo != 0ull) {
         const uint32_t b0 = (uint32_t)__builtin_ctzll(todo);
         todo &= todo - 1ull;
@@ -2002,10 +2071,18 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
     __shared__ __attribute__((aligned(16))) double s_rows[ROWS * STRIDE];
     __shared__ uint32_t s_keys[ROWS];
     __shared__ uint8_t s_touch[ROWS];
+#if RF_WIDE_MARKS
+    __shared__ uint8_t s_wide[ROWS];
+#else
+    uint8_t *const s_wide = nullptr;
+#endif
     for (uint32_t i = threadIdx.x; i < (uint32_t)(ROWS * STRIDE); i += kBlock) s_rows[i] = 0.0;
     for (uint32_t i = threadIdx.x; i < (uint32_t)ROWS; i += kBlock) {
         s_keys[i] = kNone;
         s_touch[i] = (uint8_t)0;
+#if RF_WIDE_MARKS
+        s_wide[i] = (uint8_t)0;
+#endif
     }
     __syncthreads();
 
@@ -2018,7 +2095,8 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
     uint32_t it = 0;
     bool block_alive = true;
 #ifdef RF_EXPERIMENT_SECTIONS
-    unsigned long long sec_cache = 0, sec_flush = 0, sec_steps = 0, sec_total = __builtin_readcyclecounter();
+    unsigned long long sec_cache = 0, sec_steps = 0, sec_total = __builtin_readcyclecounter();
+    FlushRecord rec;
 #endif
     while (block_alive) {
         if (ballot(W.alive) != 0ull) {
@@ -2053,6 +2131,9 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
 #pragma unroll
                         for (int k = 0; k < 3 * NB; ++k) colour = colour || (v[k] != 0.0f);
                         if (colour) {
+#if RF_WIDE_MARKS
+                            s_wide[s_row] = (uint8_t)1;
+#endif
 #pragma unroll
                             for (int k = 0; k < 3 * NB; ++k) atomicAdd(row + k, (double)v[k]);
                         }
@@ -2062,6 +2143,9 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
                         for (int k = 0; k < A; ++k)
                             if (v[k] != 0.0f) grad_add(dst + k, v[k]);
                     }
+#ifdef RF_EXPERIMENT_SECTIONS
+                    rec.bypass += (unsigned long long)__builtin_popcountll(ballot(act && s_row < 0));
+#endif
                 } else {
                     const int s_row = act ? cache_find<ROWS>(s_keys, G.cur) : -1;
                     if (act && s_row >= 0) {
@@ -2070,12 +2154,18 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
                     } else if (act) {
                         grad_add(p.attr_grad + (size_t)G.cur * p.attr_pitch + (A - 1), G.dL_ds);
                     }
+#ifdef RF_EXPERIMENT_SECTIONS
+                    rec.bypass += (unsigned long long)__builtin_popcountll(ballot(act && s_row < 0));
+#endif
                 }
                 const bool pact = G.has && G.pg_on;
                 if (ballot(pact) != 0ull) {
                     const int s_pg = pact ? cache_find<ROWS>(s_keys, G.prev) : -1;
                     if (pact && s_pg >= 0) {
                         s_touch[s_pg] = (uint8_t)1;
+#if RF_WIDE_MARKS
+                        s_wide[s_pg] = (uint8_t)1;
+#endif
                         double *dst = s_rows + s_pg * STRIDE + L::COL_PG;
                         atomicAdd(dst + 0, (double)G.px);
                         atomicAdd(dst + 1, (double)G.py);
@@ -2086,6 +2176,9 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
                         grad_add(dst + 1, G.py);
                         grad_add(dst + 2, G.pz);
                     }
+#ifdef RF_EXPERIMENT_SECTIONS
+                    rec.bypass += (unsigned long long)__builtin_popcountll(ballot(pact && s_pg < 0));
+#endif
                 }
             }
             G.has = false;
@@ -2101,23 +2194,42 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
             const unsigned long long f0 = __builtin_readcyclecounter();
 #endif
             block_alive = __syncthreads_or(W.alive ? 1 : 0) != 0;
-            cache_flush<NB>(s_rows, s_keys, s_touch, !block_alive, p.attr_grad, p.points_grad, p.attr_pitch);
+#ifdef RF_EXPERIMENT_SECTIONS
+            const unsigned long long f1 = __builtin_readcyclecounter();
+            cache_flush<NB>(s_rows, s_keys, s_touch, s_wide, !block_alive, p.attr_grad, p.points_grad, p.attr_pitch, rec);
+            const unsigned long long f2 = __builtin_readcyclecounter();
+#else
+            cache_flush<NB>(s_rows, s_keys, s_touch, s_wide, !block_alive, p.attr_grad, p.points_grad, p.attr_pitch);
+#endif
             __syncthreads();
 #ifdef RF_EXPERIMENT_SECTIONS
-            sec_flush += __builtin_readcyclecounter() - f0;
+            rec.arrive += f1 - f0;
+            rec.body += f2 - f1;
+            rec.close += __builtin_readcyclecounter() - f2;
+            rec.epochs++;
 #endif
         }
     }
 #ifdef RF_EXPERIMENT_SECTIONS
     // wave clocks per section: [8] waiting for the hop's records + face hit, [9] backward_segment, [10] merge + cache
-    // updates of the step, [11] barriers + flush of the epochs, [12] the whole walk, [13] wave-steps
+    // updates of the step, [11] barriers + flush of the epochs, [12] the whole walk, [13] wave-steps; of [11]:
+    // [14] from a wave's arrival at an epoch's first barrier to its release (with the alive vote), [15] the flush,
+    // [16] the wait at the closing barrier.  [17] wave-epochs (4 per block-epoch), rows evicted [18] wide [19] narrow,
+    // [20] lane adds that found no row and went straight to memory
     if (p.stats && (threadIdx.x & 63u) == 0u) {
         atomicAdd(p.stats + 8, W.sec_wait);
         atomicAdd(p.stats + 9, W.sec_segment);
         atomicAdd(p.stats + 10, sec_cache);
-        atomicAdd(p.stats + 11, sec_flush);
+        atomicAdd(p.stats + 11, rec.arrive + rec.body + rec.close);
         atomicAdd(p.stats + 12, (unsigned long long)__builtin_readcyclecounter() - sec_total);
         atomicAdd(p.stats + 13, sec_steps);
+        atomicAdd(p.stats + 14, rec.arrive);
+        atomicAdd(p.stats + 15, rec.body);
+        atomicAdd(p.stats + 16, rec.close);
+        atomicAdd(p.stats + 17, rec.epochs);
+        atomicAdd(p.stats + 18, rec.wide);
+        atomicAdd(p.stats + 19, rec.narrow);
+        atomicAdd(p.stats + 20, rec.bypass);
     }
 #endif
 }

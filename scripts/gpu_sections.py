@@ -17,7 +17,14 @@ from radfoam_amd import foam  # noqa: E402
 dev = torch.device("cuda:0")
 workload = os.environ.get("WORKLOAD", "train-batch")
 sh = int(os.environ.get("SH", "3" if workload == "train-batch" else "2"))
-fm = foam.make_synthetic_foam(2_000_000, sh, 5, cache_dir=foam.default_cache_dir())
+def gpu_triangulation(raw):      # as bench.py: no cached Qhull lists on a fresh clone, and Qhull takes minutes
+    from radfoam_amd import triangulation
+    _, sorted_pts = triangulation.kd_order(torch.from_numpy(raw).to(dev))
+    adj_, off_, _ = triangulation.delaunay_adjacency(sorted_pts)
+    return sorted_pts.cpu().numpy(), off_.cpu().numpy(), adj_.cpu().numpy()
+
+
+fm = foam.make_synthetic_foam(2_000_000, sh, 5, cache_dir=foam.default_cache_dir(), triangulate=gpu_triangulation)
 if os.environ.get("EMPTY_DENSITY"):     # every segment lit: bench.py --empty-density
     fm = dict(fm)
     fm["attributes"] = fm["attributes"].copy()
@@ -38,7 +45,7 @@ for _ in range(3):
     f = pipe.trace_forward(p, a, adj, off, rays, start)
     pipe.trace_backward(p, a, adj, off, rays, start, f["rgba"], g)
 torch.cuda.synchronize()
-stats = torch.zeros(16, dtype=torch.int64, device=dev)
+stats = torch.zeros(24, dtype=torch.int64, device=dev)
 pipe.experiment_stats = stats
 f = pipe.trace_forward(p, a, adj, off, rays, start)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -49,8 +56,20 @@ torch.cuda.synchronize()
 s = stats.cpu().tolist()
 tot = s[12]
 third, fourth = ("tables", "colour_rows_out") if workload == "train-batch" else ("merge_and_cache_updates", "epoch_barriers_and_flush")
-print(json.dumps({"workload": workload, "sh_degree": sh, "empty_density": os.environ.get("EMPTY_DENSITY"), "backward_ms": round(e0.elapsed_time(e1), 3), "wave_steps": s[13],
+flush = {}
+if workload != "train-batch" and s[17]:
+    # the image backward's epochs (backward_replay_cached_kernel): the three parts of "epoch_barriers_and_flush", and the
+    # rows a block evicts per epoch (a block has four waves; each counts its own epochs and the rows it owns)
+    block_epochs = s[17] / 4
+    flush = {"share_epoch_first_barrier": round(s[14] / tot, 3), "share_epoch_flush_body": round(s[15] / tot, 3),
+             "share_epoch_closing_barrier": round(s[16] / tot, 3), "block_epochs": int(block_epochs),
+             "clocks_per_wave_epoch": round((s[14] + s[15] + s[16]) / s[17], 1),
+             "evicted_rows_per_block_epoch": round((s[18] + s[19]) / block_epochs, 2),
+             "evicted_wide_rows_per_block_epoch": round(s[18] / block_epochs, 2),
+             "evicted_narrow_rows_per_block_epoch": round(s[19] / block_epochs, 2),
+             "bypass_lane_adds_per_block_epoch": round(s[20] / block_epochs, 3), "bypass_lane_adds": s[20]}
+print(json.dumps({"lib": os.path.basename(os.environ.get("RADFOAM_HIP_LIB", "libradfoam_hip.so")), "workload": workload, "sh_degree": sh, "empty_density": os.environ.get("EMPTY_DENSITY"), "backward_ms": round(e0.elapsed_time(e1), 3), "wave_steps": s[13],
                   "clocks_per_wave_step": round(tot / max(s[13], 1), 1),
                   "share_wait_records_and_face_hit": round(s[8] / tot, 3), "share_segment_colour_row_and_math": round(s[9] / tot, 3),
                   "share_" + third: round(s[10] / tot, 3), "share_" + fourth: round(s[11] / tot, 3),
-                  "share_other": round(1 - (s[8] + s[9] + s[10] + s[11]) / tot, 3)}))
+                  "share_other": round(1 - (s[8] + s[9] + s[10] + s[11]) / tot, 3), **flush}))
