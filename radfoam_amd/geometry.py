@@ -9,15 +9,18 @@
                                 ``points``
   cell_geometry_in_box          cell_geometry of the cells clipped to an axis-aligned box: every cell bounded, plus the
                                 area each cell takes of each wall
+  cell_geometry_in_box_grad     the gradient of a function of the boxed volumes and centroids with respect to ``points``
+  differentiable_cell_geometry_in_box  cell_geometry_in_box whose volume and centroid carry autograd to ``points``
   cell_moments    the second moment of every cell about its site and about its centroid: the cell's shape
   cell_moments_grad             the gradient of a function of the second moments with respect to ``points``
   differentiable_cell_moments   cell_moments whose moments, volume and centroid carry autograd to ``points``
 
 Cell ``a`` is the intersection of the half-spaces of its row of ``point_adjacency`` (taken as given); no tetrahedra are
 involved.  All take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip, csrc/rf_cell_geometry_grad.hip,
-csrc/rf_face_area_grad.hip, csrc/rf_cell_moments.hip, csrc/rf_cell_moments_grad.hip and csrc/rf_cell_box.hip behind the
-C-ABI of include/radfoam_hip_geometry.h, include/radfoam_hip_geometry_grad.h, include/radfoam_hip_face_area_grad.h,
-include/radfoam_hip_moments.h, include/radfoam_hip_moments_grad.h and include/radfoam_hip_box.h; there is no CPU path.
+csrc/rf_face_area_grad.hip, csrc/rf_cell_moments.hip, csrc/rf_cell_moments_grad.hip, csrc/rf_cell_box.hip and
+csrc/rf_cell_box_grad.hip behind the C-ABI of include/radfoam_hip_geometry.h, include/radfoam_hip_geometry_grad.h,
+include/radfoam_hip_face_area_grad.h, include/radfoam_hip_moments.h, include/radfoam_hip_moments_grad.h,
+include/radfoam_hip_box.h and include/radfoam_hip_box_grad.h; there is no CPU path.
 """
 from __future__ import annotations
 
@@ -179,10 +182,106 @@ def cell_geometry_in_box(points: torch.Tensor, point_adjacency: torch.Tensor, po
     nothing is +inf.  A site outside the box still owns what its cell cuts out of the box.  An empty cell has volume 0,
     centroid NaN, areas 0 and nonempty False (nonempty is volume > 0; a flat cell may fall on either side by rounding);
     a cell with an empty row is the whole box.  Where a wall coincides with a bisector plane the row's face keeps the area
-    and the wall gets 0.  Bit-reproducible; not differentiable.  Raises ValueError for a box that is not finite with
+    and the wall gets 0.  Bit-reproducible; not differentiable (differentiable_cell_geometry_in_box is, and
+    cell_geometry_in_box_grad is its operator).  Raises ValueError for a box that is not finite with
     lo < hi, and RuntimeError naming the cell like cell_geometry."""
     six = _box_six(box)
     return _run_geometry_in_box(*_prepare(points, point_adjacency, point_adjacency_offsets), six)[0]
+
+
+def _run_geometry_in_box_grad(p, adj, off, bbox, six, volume, centroid, nonempty, grad_volume, grad_centroid):
+    """grad_points f64[N,3]; one synchronisation, to read whether a row was refused."""
+    n, e, dev = p.size(0), adj.numel(), p.device
+    lib = _lib.load()
+    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rf_cell_box_grad_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
+    opt = lambda t: None if t is None else _ptr(t)
+    with torch.cuda.device(dev):
+        rc = lib.rf_cell_box_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), *six, _ptr(volume), _ptr(centroid),
+                                  _ptr(nonempty), opt(grad_volume), opt(grad_centroid), _ptr(grad), _ptr(status),
+                                  _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc)
+    if n:
+        worst, cell = status.max(0)
+        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
+        if worst:
+            raise RuntimeError(f"cell_geometry_in_box_grad: cell {cell} is not supported: "
+                               f"{_STATUS_TEXT.get(worst, worst)}")
+    return grad
+
+
+def cell_geometry_in_box_grad(points: torch.Tensor, point_adjacency: torch.Tensor,
+                              point_adjacency_offsets: torch.Tensor, box, geometry: BoxedCellGeometry, grad_volume,
+                              grad_centroid) -> torch.Tensor:
+    """f64[N,3]: the gradient with respect to ``points`` of  L = sum_a grad_volume[a] volume[a] + grad_centroid[a] .
+    centroid[a]  over the non-empty cells, ``geometry`` being what cell_geometry_in_box returned for the same arguments.
+    The box is fixed.
+
+    The walls do not move, so only the row's faces carry a term, each by its part inside the box:
+    grad p_a = sum over b in a's row of (1 / |p_b - p_a|) int_{F_ab n box} (phi_a - phi_b)(x) (x - p_a) dA  with
+    phi_a(x) = grad_volume[a] + (grad_centroid[a] / volume[a]) . (x - centroid[a]), and phi_a = 0 for an empty cell:
+    whatever arrives for it, NaN and inf included, is ignored, and so is its NaN centroid.  A face with an empty cell on
+    either side carries no term (its part inside the box has area zero, or the empty cell is flat against a wall), so an
+    empty cell's row is zero; a cell with an empty row gets zero; a site outside the box with a non-empty cell is an
+    ordinary row.  Either upstream (f64 or f32, [N] and [N,3]) may be None.  The polygons are the forward's (the same
+    plane list, clipping square and rule for coincident planes); where a wall coincides with a bisector plane the
+    geometry is not differentiable, and the result follows that rule and stays finite.  A flat cell that rounding made
+    ``nonempty`` has a volume of a few ulps, and ``grad_centroid / volume`` is as large as that makes it: masking such
+    cells out of the loss is the caller's concern, as in the forward.  A gather over each site's own row,
+    bit-reproducible: the exact gradient for a symmetric adjacency such as a Delaunay CSR; where a row omits a site
+    that lists it, the omitted terms are dropped.  Raises ValueError for a bad box before any tensor is looked at,
+    RuntimeError if ``geometry`` does not fit these points, and RuntimeError naming the cell like cell_geometry."""
+    six = _box_six(box)
+    p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+    n, dev = p.size(0), p.device
+    volume, centroid, nonempty = (getattr(geometry, k, None) for k in ("volume", "centroid", "nonempty"))
+    if (not all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev for t in (volume, centroid, nonempty))
+            or volume.dtype != torch.float64 or volume.shape != (n,) or centroid.dtype != torch.float64
+            or centroid.shape != (n, 3) or nonempty.dtype != torch.bool or nonempty.shape != (n,)):
+        raise RuntimeError("geometry must be the BoxedCellGeometry cell_geometry_in_box returned for these points")
+    return _run_geometry_in_box_grad(p, adj, off, bbox, six, volume.detach().contiguous(),
+                                     centroid.detach().contiguous(), nonempty.contiguous().view(torch.uint8),
+                                     _upstream("grad_volume", grad_volume, (n,), dev),
+                                     _upstream("grad_centroid", grad_centroid, (n, 3), dev))
+
+
+class _DifferentiableCellGeometryInBox(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, point_adjacency, point_adjacency_offsets, six):
+        p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+        geo = _run_geometry_in_box(p, adj, off, bbox, six)[0]
+        ctx.save_for_backward(p, adj, off, bbox, geo.volume, geo.centroid, geo.nonempty)
+        ctx.six = six
+        ctx.points_dtype = points.dtype
+        ctx.set_materialize_grads(False)      # an output the loss leaves out arrives as None and its operator is not run
+        ctx.mark_non_differentiable(geo.nonempty, geo.face_area, geo.wall_area)
+        return geo.volume, geo.centroid, geo.nonempty, geo.face_area, geo.wall_area
+
+    @staticmethod
+    def backward(ctx, grad_volume, grad_centroid, _grad_nonempty, _grad_face_area, _grad_wall_area):
+        p, adj, off, bbox, volume, centroid, nonempty = ctx.saved_tensors
+        n, dev = p.size(0), p.device
+        if grad_volume is None and grad_centroid is None:
+            grad = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        else:
+            grad = _run_geometry_in_box_grad(p, adj, off, bbox, ctx.six, volume, centroid, nonempty.view(torch.uint8),
+                                             _upstream("grad_volume", grad_volume, (n,), dev),
+                                             _upstream("grad_centroid", grad_centroid, (n, 3), dev))
+        return grad.to(ctx.points_dtype), None, None, None
+
+
+def differentiable_cell_geometry_in_box(points: torch.Tensor, point_adjacency: torch.Tensor,
+                                        point_adjacency_offsets: torch.Tensor, box) -> BoxedCellGeometry:
+    """cell_geometry_in_box, bit for bit, with ``volume`` and ``centroid`` carrying autograd to ``points``
+    (cell_geometry_in_box_grad: summed in double, returned in the dtype of ``points``); the box is fixed.  Every site
+    owns a bounded cell here, hull sites and sites outside the box included, so mass terms sum density volume, Lloyd
+    energies and equal-volume penalties reach all of them.  ``nonempty``, ``face_area`` and ``wall_area`` are not
+    differentiable, and the backward is not run for an output the loss leaves out.  Mask the empty cells out of a loss
+    (their centroid is NaN); what flows back for them is ignored."""
+    six = _box_six(box)
+    return BoxedCellGeometry(*_DifferentiableCellGeometryInBox.apply(points, point_adjacency, point_adjacency_offsets,
+                                                                     six))
 
 
 def cell_moments(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
