@@ -1,5 +1,5 @@
-"""A foam as anisotropic Gaussians: one 3-D Gaussian per bounded Voronoi cell, written as a 3DGS-layout binary PLY that
-any splat viewer or splat-based tool reads.
+"""A foam as anisotropic Gaussians: one 3-D Gaussian per bounded Voronoi cell (or, with ``--box``, one per site: every
+cell clipped to the box), written as a 3DGS-layout binary PLY that any splat viewer or splat-based tool reads.
 
 The Gaussian of cell a is the one that matches the uniform distribution on the cell up to second order: mean the
 centroid c_a, covariance C_a / V_a with C_a the cell's central second moment (``radfoam.cell_moments``).  Its scales are
@@ -11,7 +11,11 @@ Also prints the foam's true centroidal-Voronoi energy  sum_a int_{cell a} |x - p
 next to the surrogate examples/foam_lloyd.py descends,  sum_a V_a |p_a - c_a|^2  (the part of the energy a site can
 remove by moving to its centroid: tr site = tr central + V |c - p|^2).
 
-    python examples/foam_to_gaussians.py [--points 4000] [--out foam_gaussians.ply]
+Without a box the unbounded cells of the hull have no moments and are left out, of the export and of the energy.  With
+``--box lo lo lo hi hi hi`` the cells are clipped to that box (``radfoam.cell_moments_in_box``): every site whose cell
+reaches into the box has a Gaussian, the hull's large cells included, and the energy is that of the whole box.
+
+    python examples/foam_to_gaussians.py [--points 4000] [--out foam_gaussians.ply] [--box -1 -1 -1 1 1 1]
 """
 from __future__ import annotations
 
@@ -54,7 +58,8 @@ def _quaternion(rot):
 
 
 def gaussians_from_moments(moments):
-    """``moments``: a ``radfoam.CellMoments`` (CUDA or CPU tensors).  Returns a dict over the M bounded cells:
+    """``moments``: a ``radfoam.CellMoments`` or a ``radfoam.BoxedCellMoments`` (CUDA or CPU tensors).  Returns a dict
+    over the M bounded cells, or over the M non-empty cells of the boxed moments:
 
       cell      int64[M]   the cell's index
       mean      f64[M,3]   the centroid
@@ -63,7 +68,7 @@ def gaussians_from_moments(moments):
 
     so that R diag(scale^2) R^T is the covariance central_moment / volume."""
     geo = moments.geometry
-    cell = torch.nonzero(geo.bounded).reshape(-1)
+    cell = torch.nonzero(geo.nonempty if hasattr(geo, "nonempty") else geo.bounded).reshape(-1)
     cov = _symmetric(moments.central_moment[cell] / geo.volume[cell, None])
     lam, vec = torch.linalg.eigh(cov)
     flip = torch.linalg.det(vec) < 0                       # eigh promises an orthogonal matrix, not a proper one
@@ -96,9 +101,10 @@ def cell_opacity(volume, density):
     return 1.0 - torch.exp(-density.double() * 2.0 * radius)
 
 
-def run(num_points=4000, out="foam_gaussians.ply", seed=0, device="cuda:0", quiet=False):
+def run(num_points=4000, out="foam_gaussians.ply", seed=0, device="cuda:0", quiet=False, box=None):
     """Builds a foam of ``num_points`` uniform sites with the GPU triangulation, a density that falls off from the origin
-    and a colour that follows the position, writes the PLY and returns (cells written, true CVT energy, surrogate)."""
+    and a colour that follows the position, writes the PLY and returns (cells written, true CVT energy, surrogate).
+    ``box``: six numbers (lo, hi); the cells are clipped to it and every non-empty one is written."""
     import radfoam
     from radfoam_amd.triangulation import Triangulation
 
@@ -107,7 +113,10 @@ def run(num_points=4000, out="foam_gaussians.ply", seed=0, device="cuda:0", quie
     start = (torch.rand((num_points, 3), generator=gen) * 2.0 - 1.0).to(dev)
     tri = Triangulation(start)
     points = start[tri.permutation().to(torch.int64)].contiguous()
-    moments = radfoam.cell_moments(points, tri.point_adjacency(), tri.point_adjacency_offsets())
+    if box is None:
+        moments = radfoam.cell_moments(points, tri.point_adjacency(), tri.point_adjacency_offsets())
+    else:
+        moments = radfoam.cell_moments_in_box(points, tri.point_adjacency(), tri.point_adjacency_offsets(), box)
     geo = moments.geometry
     g = gaussians_from_moments(moments)
     cell = g["cell"]
@@ -130,8 +139,10 @@ def main():
     ap.add_argument("--points", type=int, default=4000)
     ap.add_argument("--out", default="foam_gaussians.ply")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--box", type=float, nargs=6, default=None, metavar=("LOX", "LOY", "LOZ", "HIX", "HIY", "HIZ"),
+                    help="clip the cells to this box: one Gaussian per site")
     args = ap.parse_args()
-    run(args.points, args.out, args.seed)
+    run(args.points, args.out, args.seed, box=args.box)
 
 
 if __name__ == "__main__":

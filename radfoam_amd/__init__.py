@@ -8,8 +8,9 @@ include/radfoam_hip.h; everything else the reference module exports is a torch/s
 package ``radfoam/`` at the repo root.
 """
 from .cells import CellEntries, cell_entries, gather_cells, reduce_entries
-from .geometry import (BoxedCellGeometry, CellGeometry, CellMoments, cell_geometry, cell_geometry_grad,
-                       cell_geometry_in_box, cell_geometry_in_box_grad, cell_moments, cell_moments_grad, cell_surface,
+from .geometry import (BoxedCellGeometry, BoxedCellMoments, CellGeometry, CellMoments, cell_geometry,
+                       cell_geometry_grad, cell_geometry_in_box, cell_geometry_in_box_grad, cell_moments,
+                       cell_moments_grad, cell_moments_in_box, cell_surface,
                        differentiable_cell_geometry, differentiable_cell_geometry_in_box, differentiable_cell_moments,
                        face_area_grad)
 from .mesh import CellMesh, cell_mesh, mesh_vertices, mesh_vertices_grad
@@ -30,5 +31,5 @@ __all__ = [
     "gather_cells", "reduce_entries", "sh_entries", "entry_weights", "face_area_grad", "CellMesh", "cell_mesh",
     "mesh_vertices", "mesh_vertices_grad", "CellMoments", "cell_moments", "cell_moments_grad",
     "differentiable_cell_moments", "BoxedCellGeometry", "cell_geometry_in_box",
-    "cell_geometry_in_box_grad", "differentiable_cell_geometry_in_box",
+    "cell_geometry_in_box_grad", "differentiable_cell_geometry_in_box", "BoxedCellMoments", "cell_moments_in_box",
 ]

@@ -14,13 +14,16 @@
   cell_moments    the second moment of every cell about its site and about its centroid: the cell's shape
   cell_moments_grad             the gradient of a function of the second moments with respect to ``points``
   differentiable_cell_moments   cell_moments whose moments, volume and centroid carry autograd to ``points``
+  cell_moments_in_box           cell_moments of the cells clipped to an axis-aligned box: every cell, hull cells and sites
+                                outside the box included, has its second moments
 
 Cell ``a`` is the intersection of the half-spaces of its row of ``point_adjacency`` (taken as given); no tetrahedra are
 involved.  All take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip, csrc/rf_cell_geometry_grad.hip,
-csrc/rf_face_area_grad.hip, csrc/rf_cell_moments.hip, csrc/rf_cell_moments_grad.hip, csrc/rf_cell_box.hip and
-csrc/rf_cell_box_grad.hip behind the C-ABI of include/radfoam_hip_geometry.h, include/radfoam_hip_geometry_grad.h,
-include/radfoam_hip_face_area_grad.h, include/radfoam_hip_moments.h, include/radfoam_hip_moments_grad.h,
-include/radfoam_hip_box.h and include/radfoam_hip_box_grad.h; there is no CPU path.
+csrc/rf_face_area_grad.hip, csrc/rf_cell_moments.hip, csrc/rf_cell_moments_grad.hip, csrc/rf_cell_box.hip,
+csrc/rf_cell_box_grad.hip and csrc/rf_cell_box_moments.hip behind the C-ABI of include/radfoam_hip_geometry.h,
+include/radfoam_hip_geometry_grad.h, include/radfoam_hip_face_area_grad.h, include/radfoam_hip_moments.h,
+include/radfoam_hip_moments_grad.h, include/radfoam_hip_box.h, include/radfoam_hip_box_grad.h and
+include/radfoam_hip_box_moments.h; there is no CPU path.
 """
 from __future__ import annotations
 
@@ -56,6 +59,12 @@ class CellMoments(NamedTuple):
     site_moment: torch.Tensor      # f64[N,6]: int (x - p)(x - p)^T dx as xx, yy, zz, xy, xz, yz; NaN for an unbounded cell
     central_moment: torch.Tensor   # f64[N,6]: the same about the centroid; NaN for an unbounded cell
     geometry: CellGeometry         # the volumes and centroids the central moment was formed with
+
+
+class BoxedCellMoments(NamedTuple):
+    site_moment: torch.Tensor      # f64[N,6]: int over cell n box of (x - p)(x - p)^T dx as xx, yy, zz, xy, xz, yz; finite
+    central_moment: torch.Tensor   # f64[N,6]: the same about the centroid; NaN for an empty cell
+    geometry: BoxedCellGeometry    # the volumes and centroids the central moment was formed with
 
 
 def _index_tensor(name, t, device):
@@ -308,6 +317,61 @@ def cell_moments(points: torch.Tensor, point_adjacency: torch.Tensor, point_adja
     site, central = _run_moments(p, adj, off, bbox, volume.detach().contiguous(), centroid.detach().contiguous(),
                                  bounded.contiguous().view(torch.uint8))
     return CellMoments(site, central, geometry)
+
+
+def _run_moments_in_box(p, adj, off, bbox, six, volume, centroid, nonempty):
+    """(site f64[N,6], central f64[N,6]); one synchronisation, to read whether a cell was refused."""
+    n, e, dev = p.size(0), adj.numel(), p.device
+    lib = _lib.load()
+    site = torch.empty((n, 6), dtype=torch.float64, device=dev)
+    central = torch.empty((n, 6), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rf_cell_box_moments_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.rf_cell_box_moments(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), *six, _ptr(volume),
+                                     _ptr(centroid), _ptr(nonempty), _ptr(site), _ptr(central), _ptr(status), _ptr(ws),
+                                     ws.numel(), _stream(dev))
+    _lib.check(rc)
+    if n:
+        worst, cell = status.max(0)
+        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
+        if worst:
+            raise RuntimeError(f"cell_moments_in_box: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    return site, central
+
+
+def cell_moments_in_box(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
+                        box, geometry: BoxedCellGeometry | None = None) -> BoxedCellMoments:
+    """The second moments of every Voronoi cell clipped to the axis-aligned ``box``, in double and relative to the site:
+    ``site_moment`` f64[N,6] is the integral of y y^T over cell(a) n box with y = x - p_a, stored as xx, yy, zz, xy, xz,
+    yz, and ``central_moment`` f64[N,6] is site_moment - V_a m m^T with m = centroid[a] - p_a, the moment about the
+    centroid, V_a and the centroid being those of cell_geometry_in_box.
+
+    Every cell is a bounded polytope in the box, so every site has its moments, hull sites and sites outside the box
+    included (a site outside still owns what its cell cuts out of the box; the faces' pyramids over it are signed): the
+    trace of ``site_moment`` summed over all sites is the centroidal-Voronoi energy of the box, and ``central_moment /
+    volume`` is the covariance of the uniform distribution on the clipped cell, one Gaussian per non-empty cell.  For a
+    site far outside the box V m m^T nearly cancels site_moment, and the central moment keeps fewer digits than
+    site_moment does.  An exactly empty cell has site_moment 0; ``central_moment`` is NaN wherever ``nonempty`` is
+    False; a cell with an empty row is the whole box.  ``box`` is as for cell_geometry_in_box.  ``geometry`` is what
+    cell_geometry_in_box returned for the same arguments; when it is None cell_geometry_in_box runs first, and either way
+    it comes back as the third field.  A gather over each site's own row, bit-reproducible.  Not differentiable: the
+    gradient of the boxed moments with respect to the points is not built yet.  Raises ValueError for a box that is not
+    finite with lo < hi before any tensor is looked at, RuntimeError if ``geometry`` does not fit these points, and
+    RuntimeError naming the cell like cell_geometry."""
+    six = _box_six(box)
+    p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+    n, dev = p.size(0), p.device
+    if geometry is None:
+        geometry = _run_geometry_in_box(p, adj, off, bbox, six)[0]
+    volume, centroid, nonempty = (getattr(geometry, k, None) for k in ("volume", "centroid", "nonempty"))
+    if (not all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev for t in (volume, centroid, nonempty))
+            or volume.dtype != torch.float64 or volume.shape != (n,) or centroid.dtype != torch.float64
+            or centroid.shape != (n, 3) or nonempty.dtype != torch.bool or nonempty.shape != (n,)):
+        raise RuntimeError("geometry must be the BoxedCellGeometry cell_geometry_in_box returned for these points")
+    site, central = _run_moments_in_box(p, adj, off, bbox, six, volume.detach().contiguous(),
+                                        centroid.detach().contiguous(), nonempty.contiguous().view(torch.uint8))
+    return BoxedCellMoments(site, central, geometry)
 
 
 def cell_surface(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
