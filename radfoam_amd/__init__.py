@@ -10,9 +10,9 @@ package ``radfoam/`` at the repo root.
 from .cells import CellEntries, cell_entries, gather_cells, reduce_entries
 from .geometry import (BoxedCellGeometry, BoxedCellMoments, CellGeometry, CellMoments, cell_geometry,
                        cell_geometry_grad, cell_geometry_in_box, cell_geometry_in_box_grad, cell_moments,
-                       cell_moments_grad, cell_moments_in_box, cell_surface,
+                       cell_moments_grad, cell_moments_in_box, cell_moments_in_box_grad, cell_surface,
                        differentiable_cell_geometry, differentiable_cell_geometry_in_box, differentiable_cell_moments,
-                       face_area_grad)
+                       differentiable_cell_moments_in_box, face_area_grad)
 from .mesh import CellMesh, cell_mesh, mesh_vertices, mesh_vertices_grad
 from .pipeline import Pipeline, create_pipeline, invalidate_caches
 from .scene_ops import pack_attributes
@@ -32,4 +32,5 @@ __all__ = [
     "mesh_vertices", "mesh_vertices_grad", "CellMoments", "cell_moments", "cell_moments_grad",
     "differentiable_cell_moments", "BoxedCellGeometry", "cell_geometry_in_box",
     "cell_geometry_in_box_grad", "differentiable_cell_geometry_in_box", "BoxedCellMoments", "cell_moments_in_box",
+    "cell_moments_in_box_grad", "differentiable_cell_moments_in_box",
 ]

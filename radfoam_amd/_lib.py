@@ -168,6 +168,8 @@ SYMBOLS = {
     "rf_cell_box_grad": (_INT, [_P, _U32, _P, _P, _U32, _P] + [C.c_double] * 6 + [_P] * 8 + [C.c_size_t, _P]),
     "rf_cell_box_moments_workspace_bytes": (C.c_size_t, [_U32]),
     "rf_cell_box_moments": (_INT, [_P, _U32, _P, _P, _U32, _P] + [C.c_double] * 6 + [_P] * 7 + [C.c_size_t, _P]),
+    "rf_cell_box_moments_grad_workspace_bytes": (C.c_size_t, [_U32]),
+    "rf_cell_box_moments_grad": (_INT, [_P, _U32, _P, _P, _U32, _P] + [C.c_double] * 6 + [_P] * 10 + [C.c_size_t, _P]),
 }
 
 _lib = None

@@ -16,14 +16,18 @@
   differentiable_cell_moments   cell_moments whose moments, volume and centroid carry autograd to ``points``
   cell_moments_in_box           cell_moments of the cells clipped to an axis-aligned box: every cell, hull cells and sites
                                 outside the box included, has its second moments
+  cell_moments_in_box_grad      the gradient of a function of the boxed second moments, volumes and centroids with respect
+                                to ``points``, in one launch
+  differentiable_cell_moments_in_box  cell_moments_in_box whose moments, volume and centroid carry autograd to ``points``
 
 Cell ``a`` is the intersection of the half-spaces of its row of ``point_adjacency`` (taken as given); no tetrahedra are
 involved.  All take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip, csrc/rf_cell_geometry_grad.hip,
 csrc/rf_face_area_grad.hip, csrc/rf_cell_moments.hip, csrc/rf_cell_moments_grad.hip, csrc/rf_cell_box.hip,
-csrc/rf_cell_box_grad.hip and csrc/rf_cell_box_moments.hip behind the C-ABI of include/radfoam_hip_geometry.h,
+csrc/rf_cell_box_grad.hip, csrc/rf_cell_box_moments.hip and csrc/rf_cell_box_moments_grad.hip behind the C-ABI of
+include/radfoam_hip_geometry.h,
 include/radfoam_hip_geometry_grad.h, include/radfoam_hip_face_area_grad.h, include/radfoam_hip_moments.h,
-include/radfoam_hip_moments_grad.h, include/radfoam_hip_box.h, include/radfoam_hip_box_grad.h and
-include/radfoam_hip_box_moments.h; there is no CPU path.
+include/radfoam_hip_moments_grad.h, include/radfoam_hip_box.h, include/radfoam_hip_box_grad.h,
+include/radfoam_hip_box_moments.h and include/radfoam_hip_box_moments_grad.h; there is no CPU path.
 """
 from __future__ import annotations
 
@@ -355,9 +359,10 @@ def cell_moments_in_box(points: torch.Tensor, point_adjacency: torch.Tensor, poi
     site_moment does.  An exactly empty cell has site_moment 0; ``central_moment`` is NaN wherever ``nonempty`` is
     False; a cell with an empty row is the whole box.  ``box`` is as for cell_geometry_in_box.  ``geometry`` is what
     cell_geometry_in_box returned for the same arguments; when it is None cell_geometry_in_box runs first, and either way
-    it comes back as the third field.  A gather over each site's own row, bit-reproducible.  Not differentiable: the
-    gradient of the boxed moments with respect to the points is not built yet.  Raises ValueError for a box that is not
-    finite with lo < hi before any tensor is looked at, RuntimeError if ``geometry`` does not fit these points, and
+    it comes back as the third field.  A gather over each site's own row, bit-reproducible.  Not differentiable itself:
+    differentiable_cell_moments_in_box carries autograd to the points, and cell_moments_in_box_grad is its operator
+    (the gradient with respect to the box is not built yet).  Raises ValueError for a box that is not finite with
+    lo < hi before any tensor is looked at, RuntimeError if ``geometry`` does not fit these points, and
     RuntimeError naming the cell like cell_geometry."""
     six = _box_six(box)
     p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
@@ -657,3 +662,122 @@ def differentiable_cell_geometry(points: torch.Tensor, point_adjacency: torch.Te
     volume and area are +inf and their centroid NaN); what flows back for them is ignored."""
     return CellGeometry(*_DifferentiableCellGeometry.apply(points, point_adjacency, point_adjacency_offsets,
                                                            bool(face_area)))
+
+
+def _run_moments_in_box_grad(p, adj, off, bbox, six, volume, centroid, nonempty, grad_site_moment, grad_central_moment,
+                             grad_volume, grad_centroid):
+    """grad_points f64[N,3]; one launch of the fused operator and one synchronisation, to read whether a row was
+    refused."""
+    n, e, dev = p.size(0), adj.numel(), p.device
+    lib = _lib.load()
+    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rf_cell_box_moments_grad_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
+    opt = lambda t: None if t is None else _ptr(t)
+    with torch.cuda.device(dev):
+        rc = lib.rf_cell_box_moments_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), *six, _ptr(volume),
+                                          _ptr(centroid), _ptr(nonempty), opt(grad_site_moment),
+                                          opt(grad_central_moment), opt(grad_volume), opt(grad_centroid), _ptr(grad),
+                                          _ptr(status), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc)
+    if n:
+        worst, cell = status.max(0)
+        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
+        if worst:
+            raise RuntimeError(f"cell_moments_in_box_grad: cell {cell} is not supported: "
+                               f"{_STATUS_TEXT.get(worst, worst)}")
+    return grad
+
+
+def cell_moments_in_box_grad(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
+                             box, geometry: BoxedCellGeometry, grad_site_moment=None, grad_central_moment=None,
+                             grad_volume=None, grad_centroid=None) -> torch.Tensor:
+    """f64[N,3]: the gradient with respect to ``points`` of  L = sum_a <grad_site_moment[a], site_moment[a]> +
+    <grad_central_moment[a], central_moment[a]> + grad_volume[a] volume[a] + grad_centroid[a] . centroid[a]  over the
+    non-empty cells of cell_moments_in_box, each bracket the plain sum over the six stored numbers (xx, yy, zz, xy, xz,
+    yz), ``geometry`` being what cell_geometry_in_box returned for the same arguments.  The box is fixed.  One launch
+    for all four upstreams: a loss that mixes moments with volume or centroid terms clips every face once.
+
+    With G_a and H_a the symmetric matrices of the two moment upstreams (the diagonal as it is, half of each off-diagonal
+    number on both sides) and Psi_a(x) = (x - p_a)^T G_a (x - p_a) + (x - c_a)^T H_a (x - c_a) + grad_volume[a] +
+    (grad_centroid[a] / volume[a]) . (x - c_a), Psi_a = 0 for an empty cell (whatever arrives for it, NaN and inf
+    included, is ignored, and so is its NaN centroid),
+    grad p_a = sum over b in a's row of (1 / |p_b - p_a|) int_{F_ab n box} (Psi_a - Psi_b)(x) (x - p_a) dA  -  2 V_a G_a
+    (c_a - p_a).  The walls do not move, so only the row's faces carry a boundary term, each by its part inside the box.
+    The last, direct term is the site moment's alone (the central moment has none, because c_a is the centroid of the
+    clipped cell, nor have the volume and the centroid) and is there whenever the cell is non-empty, also for an empty
+    row: that cell is the whole box, and grad p_a = -2 V_box G_a (centre - p_a).  A face with an empty cell on either side
+    carries no term, so an empty cell's row is zero; a site outside the box with a non-empty cell is an ordinary row.
+    Any of the four upstreams (f64 or f32; [N,6], [N,6], [N], [N,3]) may be None.  The polygons are the forward's (the
+    same plane list, clipping square and rule for coincident planes); where a wall coincides with a bisector plane the
+    geometry is not differentiable, and the result follows that rule and stays finite.  A flat cell that rounding made
+    ``nonempty`` has a volume of a few ulps, and ``grad_centroid / volume`` is as large as that makes it: masking such
+    cells out of the loss is the caller's concern, as in the forward.  A gather over each site's own row,
+    bit-reproducible: the exact gradient for a symmetric adjacency such as a Delaunay CSR; where a row omits a site that
+    lists it, the omitted terms are dropped.  Raises ValueError for a bad box before any tensor is looked at, RuntimeError
+    if ``geometry`` does not fit these points, and RuntimeError naming the cell like cell_geometry."""
+    six = _box_six(box)
+    p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+    n, dev = p.size(0), p.device
+    volume, centroid, nonempty = (getattr(geometry, k, None) for k in ("volume", "centroid", "nonempty"))
+    if (not all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev for t in (volume, centroid, nonempty))
+            or volume.dtype != torch.float64 or volume.shape != (n,) or centroid.dtype != torch.float64
+            or centroid.shape != (n, 3) or nonempty.dtype != torch.bool or nonempty.shape != (n,)):
+        raise RuntimeError("geometry must be the BoxedCellGeometry cell_geometry_in_box returned for these points")
+    return _run_moments_in_box_grad(p, adj, off, bbox, six, volume.detach().contiguous(),
+                                    centroid.detach().contiguous(), nonempty.contiguous().view(torch.uint8),
+                                    _upstream("grad_site_moment", grad_site_moment, (n, 6), dev),
+                                    _upstream("grad_central_moment", grad_central_moment, (n, 6), dev),
+                                    _upstream("grad_volume", grad_volume, (n,), dev),
+                                    _upstream("grad_centroid", grad_centroid, (n, 3), dev))
+
+
+class _DifferentiableCellMomentsInBox(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, point_adjacency, point_adjacency_offsets, six):
+        p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+        geo = _run_geometry_in_box(p, adj, off, bbox, six)[0]
+        site, central = _run_moments_in_box(p, adj, off, bbox, six, geo.volume, geo.centroid,
+                                            geo.nonempty.view(torch.uint8))
+        ctx.save_for_backward(p, adj, off, bbox, geo.volume, geo.centroid, geo.nonempty)
+        ctx.six = six
+        ctx.points_dtype = points.dtype
+        ctx.set_materialize_grads(False)      # an output the loss leaves out arrives as None and its operator is not run
+        ctx.mark_non_differentiable(geo.nonempty, geo.face_area, geo.wall_area)
+        return site, central, geo.volume, geo.centroid, geo.nonempty, geo.face_area, geo.wall_area
+
+    @staticmethod
+    def backward(ctx, grad_site, grad_central, grad_volume, grad_centroid, _grad_nonempty, _grad_face_area,
+                 _grad_wall_area):
+        p, adj, off, bbox, volume, centroid, nonempty = ctx.saved_tensors
+        n, dev = p.size(0), p.device
+        flags = nonempty.view(torch.uint8)
+        gv = _upstream("grad_volume", grad_volume, (n,), dev)
+        gc = _upstream("grad_centroid", grad_centroid, (n, 3), dev)
+        if grad_site is not None or grad_central is not None:      # one launch with every upstream that is present
+            grad = _run_moments_in_box_grad(p, adj, off, bbox, ctx.six, volume, centroid, flags,
+                                            _upstream("grad_site_moment", grad_site, (n, 6), dev),
+                                            _upstream("grad_central_moment", grad_central, (n, 6), dev), gv, gc)
+        elif gv is not None or gc is not None:
+            grad = _run_geometry_in_box_grad(p, adj, off, bbox, ctx.six, volume, centroid, flags, gv, gc)
+        else:
+            grad = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        return grad.to(ctx.points_dtype), None, None, None
+
+
+def differentiable_cell_moments_in_box(points: torch.Tensor, point_adjacency: torch.Tensor,
+                                       point_adjacency_offsets: torch.Tensor, box) -> BoxedCellMoments:
+    """cell_moments_in_box, bit for bit, with ``site_moment``, ``central_moment``, ``geometry.volume`` and
+    ``geometry.centroid`` carrying autograd to ``points``; the box is fixed.  Every site owns a bounded cell here, hull
+    sites and sites outside the box included: the trace of ``site_moment`` summed over all sites, the centroidal-Voronoi
+    energy of the whole box, and ``central_moment / volume[:, None]``, the covariance, are differentiable end to end and
+    reach every site.  When a moment upstream is present the backward is ONE launch of cell_moments_in_box_grad with
+    every upstream that is present, so a loss that mixes moments with volume or centroid terms pays for the clipping
+    once; with only volume and centroid upstreams it is cell_geometry_in_box_grad, bit for bit what
+    differentiable_cell_geometry_in_box gives; for an output the loss leaves out nothing is run.  Summed in double,
+    returned in the dtype of ``points``.  ``geometry.nonempty``, ``geometry.face_area`` and ``geometry.wall_area`` are not
+    differentiable.  Mask the empty cells out of a loss (their central moment and centroid are NaN); what flows back for
+    them is ignored."""
+    six = _box_six(box)
+    site, central, *geo = _DifferentiableCellMomentsInBox.apply(points, point_adjacency, point_adjacency_offsets, six)
+    return BoxedCellMoments(site, central, BoxedCellGeometry(*geo))
