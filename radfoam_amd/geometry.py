@@ -10,7 +10,9 @@
   cell_geometry_in_box          cell_geometry of the cells clipped to an axis-aligned box: every cell bounded, plus the
                                 area each cell takes of each wall
   cell_geometry_in_box_grad     the gradient of a function of the boxed volumes and centroids with respect to ``points``
-  differentiable_cell_geometry_in_box  cell_geometry_in_box whose volume and centroid carry autograd to ``points``
+  face_area_in_box_grad         the gradient of a function of the boxed face and wall areas with respect to ``points``
+  differentiable_cell_geometry_in_box  cell_geometry_in_box whose volume and centroid (and, on request, face and wall
+                                areas) carry autograd to ``points``
   cell_moments    the second moment of every cell about its site and about its centroid: the cell's shape
   cell_moments_grad             the gradient of a function of the second moments with respect to ``points``
   differentiable_cell_moments   cell_moments whose moments, volume and centroid carry autograd to ``points``
@@ -23,11 +25,13 @@
 Cell ``a`` is the intersection of the half-spaces of its row of ``point_adjacency`` (taken as given); no tetrahedra are
 involved.  All take CUDA (HIP) tensors and run the kernels of csrc/rf_cell_geometry.hip, csrc/rf_cell_geometry_grad.hip,
 csrc/rf_face_area_grad.hip, csrc/rf_cell_moments.hip, csrc/rf_cell_moments_grad.hip, csrc/rf_cell_box.hip,
-csrc/rf_cell_box_grad.hip, csrc/rf_cell_box_moments.hip and csrc/rf_cell_box_moments_grad.hip behind the C-ABI of
+csrc/rf_cell_box_grad.hip, csrc/rf_cell_box_moments.hip, csrc/rf_cell_box_moments_grad.hip and
+csrc/rf_cell_box_area_grad.hip behind the C-ABI of
 include/radfoam_hip_geometry.h,
 include/radfoam_hip_geometry_grad.h, include/radfoam_hip_face_area_grad.h, include/radfoam_hip_moments.h,
 include/radfoam_hip_moments_grad.h, include/radfoam_hip_box.h, include/radfoam_hip_box_grad.h,
-include/radfoam_hip_box_moments.h and include/radfoam_hip_box_moments_grad.h; there is no CPU path.
+include/radfoam_hip_box_moments.h, include/radfoam_hip_box_moments_grad.h and include/radfoam_hip_box_area_grad.h; there
+is no CPU path.
 """
 from __future__ import annotations
 
@@ -259,42 +263,120 @@ def cell_geometry_in_box_grad(points: torch.Tensor, point_adjacency: torch.Tenso
                                      _upstream("grad_centroid", grad_centroid, (n, 3), dev))
 
 
+def _run_face_area_in_box_grad(p, adj, off, bbox, six, volume, centroid, nonempty, face_area, wall_area, grad_face_area,
+                                grad_wall_area):
+    """grad_points f64[N,3]; one synchronisation, to read whether a row was refused."""
+    n, e, dev = p.size(0), adj.numel(), p.device
+    lib = _lib.load()
+    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(lib.rf_cell_box_area_grad_workspace_bytes(n, e)), 256), dtype=torch.uint8, device=dev)
+    opt = lambda t: None if t is None else _ptr(t)
+    with torch.cuda.device(dev):
+        rc = lib.rf_cell_box_area_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), *six, _ptr(volume),
+                                       _ptr(centroid), _ptr(nonempty), _ptr(face_area), _ptr(wall_area),
+                                       opt(grad_face_area), opt(grad_wall_area), _ptr(grad), _ptr(status), _ptr(ws),
+                                       ws.numel(), _stream(dev))
+    _lib.check(rc)
+    if n:
+        worst, cell = status.max(0)
+        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
+        if worst:
+            raise RuntimeError(f"face_area_in_box_grad: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    return grad
+
+
+def face_area_in_box_grad(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
+                          box, geometry: BoxedCellGeometry, grad_face_area=None, grad_wall_area=None) -> torch.Tensor:
+    """f64[N,3]: the gradient with respect to ``points`` of  L = sum_s grad_face_area[s] face_area[s] + sum_{a,w}
+    grad_wall_area[a,w] wall_area[a,w],  ``geometry`` being what cell_geometry_in_box returned for the same arguments.
+    The box is fixed.
+
+    In the box every face is a bounded polygon, so the gradient reaches every site, hull sites and sites outside the box
+    included (face_area_grad only reaches faces between bounded cells).  An upstream counts where that slot's or wall's
+    own forward area is > 0 and is ignored where it is exactly 0, NaN and inf included: an exactly empty cell has every
+    area 0.  Face {a,b} weighs G_ab = g[a->b] + g[b->a].  A flat face changes its area through the in-plane motion of its
+    edges, and every edge lies on a's own clipped polytope: a Voronoi edge, dual to a Delaunay triangle (a,b,c), adds
+    l (lambda_b + lambda_c) (y - p_a)  as in face_area_grad, l and y the length and midpoint of the segment as the box
+    clipped it; the trace of the bisector of (a,b) in wall w, which bounds face {a,b} and the two cells' parts of the
+    wall, adds  (l (y - p_a) / |p_b - p_a|) [ -G_ab cot t + (gw[a,w] - gw[b,w]) / sin t ]  with cos t = n_w . (p_b - p_a)
+    / |p_b - p_a| and n_w the wall's outward normal; edges between two walls do not move ("Point gradients of
+    the face and wall areas in a box").  An empty row and an empty cell get a zero row.  Either upstream (f64 or f32,
+    [E] and [N,6]) may be None, which is an all-zero upstream bit for bit.  The polygons are the forward's (the same plane
+    list, clipping square and rule for coincident planes); where a wall coincides with a bisector plane the areas are not
+    differentiable, and the result follows that rule and stays finite.  A gather over each site's own row with look-ups
+    in its neighbours', bit-reproducible: the exact gradient for a symmetric adjacency such as a Delaunay CSR; where a
+    mate slot or the slot b->c does not exist its weight is 0.  Raises ValueError for a bad box before any tensor is
+    looked at, RuntimeError if ``geometry`` does not fit these points, and RuntimeError naming the cell like
+    cell_geometry."""
+    six = _box_six(box)
+    p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
+    n, e, dev = p.size(0), adj.numel(), p.device
+    volume, centroid, nonempty, face_area, wall_area = (getattr(geometry, k, None) for k in (
+        "volume", "centroid", "nonempty", "face_area", "wall_area"))
+    if (not all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev
+                for t in (volume, centroid, nonempty, face_area, wall_area))
+            or volume.dtype != torch.float64 or volume.shape != (n,) or centroid.dtype != torch.float64
+            or centroid.shape != (n, 3) or nonempty.dtype != torch.bool or nonempty.shape != (n,)
+            or face_area.dtype != torch.float64 or face_area.shape != (e,) or wall_area.dtype != torch.float64
+            or wall_area.shape != (n, 6)):
+        raise RuntimeError("geometry must be the BoxedCellGeometry cell_geometry_in_box returned for these points")
+    return _run_face_area_in_box_grad(p, adj, off, bbox, six, volume.detach().contiguous(),
+                                      centroid.detach().contiguous(), nonempty.contiguous().view(torch.uint8),
+                                      face_area.detach().contiguous(), wall_area.detach().contiguous(),
+                                      _upstream("grad_face_area", grad_face_area, (e,), dev),
+                                      _upstream("grad_wall_area", grad_wall_area, (n, 6), dev))
+
+
 class _DifferentiableCellGeometryInBox(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, points, point_adjacency, point_adjacency_offsets, six):
+    def forward(ctx, points, point_adjacency, point_adjacency_offsets, six, with_face_area):
         p, adj, off, bbox = _prepare(points, point_adjacency, point_adjacency_offsets)
         geo = _run_geometry_in_box(p, adj, off, bbox, six)[0]
-        ctx.save_for_backward(p, adj, off, bbox, geo.volume, geo.centroid, geo.nonempty)
+        ctx.save_for_backward(p, adj, off, bbox, geo.volume, geo.centroid, geo.nonempty, geo.face_area, geo.wall_area)
         ctx.six = six
         ctx.points_dtype = points.dtype
         ctx.set_materialize_grads(False)      # an output the loss leaves out arrives as None and its operator is not run
-        ctx.mark_non_differentiable(geo.nonempty, geo.face_area, geo.wall_area)
+        if with_face_area:
+            ctx.mark_non_differentiable(geo.nonempty)
+        else:
+            ctx.mark_non_differentiable(geo.nonempty, geo.face_area, geo.wall_area)
         return geo.volume, geo.centroid, geo.nonempty, geo.face_area, geo.wall_area
 
     @staticmethod
-    def backward(ctx, grad_volume, grad_centroid, _grad_nonempty, _grad_face_area, _grad_wall_area):
-        p, adj, off, bbox, volume, centroid, nonempty = ctx.saved_tensors
-        n, dev = p.size(0), p.device
-        if grad_volume is None and grad_centroid is None:
-            grad = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-        else:
-            grad = _run_geometry_in_box_grad(p, adj, off, bbox, ctx.six, volume, centroid, nonempty.view(torch.uint8),
+    def backward(ctx, grad_volume, grad_centroid, _grad_nonempty, grad_face_area, grad_wall_area):
+        p, adj, off, bbox, volume, centroid, nonempty, face_area, wall_area = ctx.saved_tensors
+        n, e, dev = p.size(0), adj.numel(), p.device
+        flags = nonempty.view(torch.uint8)
+        grad = None
+        if grad_volume is not None or grad_centroid is not None:
+            grad = _run_geometry_in_box_grad(p, adj, off, bbox, ctx.six, volume, centroid, flags,
                                              _upstream("grad_volume", grad_volume, (n,), dev),
                                              _upstream("grad_centroid", grad_centroid, (n, 3), dev))
-        return grad.to(ctx.points_dtype), None, None, None
+        if grad_face_area is not None or grad_wall_area is not None:
+            part = _run_face_area_in_box_grad(p, adj, off, bbox, ctx.six, volume, centroid, flags, face_area, wall_area,
+                                              _upstream("grad_face_area", grad_face_area, (e,), dev),
+                                              _upstream("grad_wall_area", grad_wall_area, (n, 6), dev))
+            grad = part if grad is None else grad + part
+        if grad is None:
+            grad = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        return grad.to(ctx.points_dtype), None, None, None, None
 
 
 def differentiable_cell_geometry_in_box(points: torch.Tensor, point_adjacency: torch.Tensor,
-                                        point_adjacency_offsets: torch.Tensor, box) -> BoxedCellGeometry:
+                                        point_adjacency_offsets: torch.Tensor, box,
+                                        face_area: bool = False) -> BoxedCellGeometry:
     """cell_geometry_in_box, bit for bit, with ``volume`` and ``centroid`` carrying autograd to ``points``
     (cell_geometry_in_box_grad: summed in double, returned in the dtype of ``points``); the box is fixed.  Every site
     owns a bounded cell here, hull sites and sites outside the box included, so mass terms sum density volume, Lloyd
-    energies and equal-volume penalties reach all of them.  ``nonempty``, ``face_area`` and ``wall_area`` are not
-    differentiable, and the backward is not run for an output the loss leaves out.  Mask the empty cells out of a loss
-    (their centroid is NaN); what flows back for them is ignored."""
+    energies and equal-volume penalties reach all of them.  With ``face_area=True`` the face areas and the wall areas
+    carry autograd as well (face_area_in_box_grad); the backward runs each operator only where something arrived and adds
+    the two in double, cell_geometry_in_box_grad's result first.  By default ``nonempty``, ``face_area`` and ``wall_area``
+    are not differentiable, and the backward is not run for an output the loss leaves out.  Mask the empty cells out of
+    a loss (their centroid is NaN); what flows back for them is ignored."""
     six = _box_six(box)
     return BoxedCellGeometry(*_DifferentiableCellGeometryInBox.apply(points, point_adjacency, point_adjacency_offsets,
-                                                                     six))
+                                                                     six, bool(face_area)))
 
 
 def cell_moments(points: torch.Tensor, point_adjacency: torch.Tensor, point_adjacency_offsets: torch.Tensor,
