@@ -34,7 +34,7 @@ EXTRA_HEADERS = [os.path.join(_CSRC, n) for n in ("rf_clip.hpp", "rf_clip_grad.h
                                                       "rf_clip_moments_grad.hpp", "rf_clip_box.hpp",
                                                       "rf_clip_box_grad.hpp", "rf_clip_box_moments.hpp",
                                                       "rf_clip_box_moments_grad.hpp",
-                                                      "rf_clip_box_area_grad.hpp")] + [
+                                                      "rf_clip_box_area_grad.hpp", "rf_cell_wave.hpp")] + [
     os.path.join(os.path.dirname(_HERE), "include", n) for n in ("radfoam_hip_geometry.h", "radfoam_hip_segments.h",
                                                                "radfoam_hip_composite.h",
                                                                "radfoam_hip_geometry_grad.h",

@@ -1,16 +1,12 @@
 // rf_cell_box.hip -- Voronoi cells clipped to an axis-aligned box: volume, centroid, the part of every face inside the
 // box and the part of every wall that bounds the cell ("Cells clipped to a box").  The definition, the plane
-// list, the wall frames and the tie rule of coincident planes: rf_clip_box.hpp, all in double.
+// list, the wall frames and the tie rule of coincident planes: rf_clip_box.hpp, all in double.  The wave scheme, its LDS
+// layout and the hand-off through redo[cell]: rf_cell_wave.hpp.
 //
-//   cell_box_kernel       one wave per cell, one lane per face of the cell's list: the row's lanes first, then six wall
-//                         lanes.  The list's planes {d, h} are staged once in LDS; each lane clips its face's square by the
-//                         other planes in list order, its polygon in an LDS slot (vertex-major, lanes side by side; no
-//                         per-lane arrays).  Volume and first moments are wave reductions.  Takes lists of up to 64 planes
-//                         (rows of up to 58) whose polygons stay within kLaneCap vertices; anything else it hands on,
-//                         untouched, through redo[cell].
-//   cell_box_redo_kernel  one wave per 64 cells: the cells handed on are walked by lane 0, face after face
-//                         (rf::clip::cell_box_serial, what the host harness runs), with kWaveCap vertices.  Beyond that
-//                         the cell's status says so and the caller raises.
+//   cell_box_kernel       one lane per face of the cell's list: the row's lanes first, then six wall lanes; each lane
+//                         clips its face's square by the other planes in list order.  Volume and first moments are wave
+//                         reductions.  Lists of up to 64 planes (rows of up to 58).
+//   cell_box_redo_kernel  the cells handed on, by rf::clip::cell_box_serial.
 //
 // Every output element is written exactly once, by plain stores; no atomics: the result is bit-reproducible.
 #include <hip/hip_runtime.h>
@@ -18,21 +14,10 @@
 #include <stdint.h>
 
 #include "../../include/radfoam_hip_box.h"
-#include "rf_clip_box.hpp"
-#include "rf_host.hpp"
+#include "rf_cell_wave.hpp"
 
 namespace rf {
 namespace cell_box {
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kLaneCap = 16;    // as cell_geometry_kernel: 32 KiB of polygons per wave
-constexpr uint32_t kWaveCap = 256;   // as cell_geometry_redo_kernel
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(64) void cell_box_kernel(
     const float *__restrict__ points, uint32_t num_points, const uint32_t *__restrict__ adj,
@@ -47,18 +32,18 @@ __global__ __launch_bounds__(64) void cell_box_kernel(
     const clip::Box box = {lo_x, lo_y, lo_z, hi_x, hi_y, hi_z};
     const uint32_t a = blockIdx.x, lane = threadIdx.x;
     const uint32_t begin = offsets[a], end = offsets[a + 1];
-    if (begin > end || end > num_edges || end - begin > kWave - clip::kWalls) {   // wave-uniform
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (begin > end || end > num_edges || end - begin > kWave - clip::kWalls)   // wave-uniform
+        return hand_on(redo, a, lane);
     const uint32_t degree = end - begin, count = degree + clip::kWalls;
     if (degree == 0) {   // no neighbours: the whole box
         if (lane == 0) {
             clip::whole_box(box, a, volume, centroid, nonempty, wall_area, wall_vertices);
-            redo[a] = 0;
+            keep(redo, a);
         }
         return;
     }
+    // the staging with the walls as lanes, spelled out: through a shared helper the wall test moves in the kernel's code.
+    // The load and the bad test are load_neighbour's of rf_cell_wave.hpp, line for line: keep the two in step.
     const bool row = lane < degree, wall = !row && lane < count;
     uint32_t q = row ? adj[begin + lane] : 0u;
     bool bad = row && (q >= num_points || q == a);
@@ -68,11 +53,7 @@ __global__ __launch_bounds__(64) void cell_box_kernel(
     bad = bad || (row && !(h > 0.0));
     if (wall) clip::wall_plane(points, a, box, lane - degree, dx, dy, dz, h);
     s_plane[0][lane] = dx, s_plane[1][lane] = dy, s_plane[2][lane] = dz, s_plane[3][lane] = h;
-    __syncthreads();
-    if (__any(bad)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (sync_any_bad(bad)) return hand_on(redo, a, lane);
     const double R = clip::half_side_box(bbox, box);
     bool overflow = false;
     double area = 0.0;
@@ -84,7 +65,7 @@ __global__ __launch_bounds__(64) void cell_box_kernel(
         clip::init_square(s, t, kWave, R);
         m = 4;
         uint32_t cur = 0;
-        for (uint32_t j = 0; j < count && m != 0; ++j) {
+        for (uint32_t j = 0; j < count && m != 0; ++j) {   // by the other planes of the list, in list order
             if (j == lane) continue;
             if (!clip::clip_by_list_plane(frame, dx, dy, dz, j < lane, s_plane[0][j], s_plane[1][j], s_plane[2][j],
                                           s_plane[3][j], s, t, kWave, kLaneCap, m, cur)) {
@@ -99,10 +80,7 @@ __global__ __launch_bounds__(64) void cell_box_kernel(
             clip::add_face_box(sums, frame, wall, h, area, cs, ct);
         }
     }
-    if (__any(overflow)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (__any(overflow)) return hand_on(redo, a, lane);
     if (row) {
         face_area[begin + lane] = area;
         face_vertices[begin + lane] = m;
@@ -114,7 +92,7 @@ __global__ __launch_bounds__(64) void cell_box_kernel(
     sums.mx = wave_sum(sums.mx), sums.my = wave_sum(sums.my), sums.mz = wave_sum(sums.mz);
     if (lane == 0) {
         clip::write_cell_box(points, a, sums, volume, centroid, nonempty);
-        redo[a] = 0;
+        keep(redo, a);
     }
 }
 
@@ -127,15 +105,11 @@ __global__ __launch_bounds__(64) void cell_box_redo_kernel(
     uint32_t *__restrict__ wall_vertices, const uint8_t *__restrict__ redo, uint8_t *__restrict__ cell_status) {
     __shared__ double s_s[2 * kWaveCap], s_t[2 * kWaveCap];
     const clip::Box box = {lo_x, lo_y, lo_z, hi_x, hi_y, hi_z};
-    const uint32_t cell = blockIdx.x * kWave + threadIdx.x;
-    const bool mine = cell < num_points && redo[cell] != 0;
-    if (cell < num_points && !mine) cell_status[cell] = (uint8_t)clip::kCellOk;
-    unsigned long long todo = __ballot(mine);
+    unsigned long long todo = redo_todo(num_points, redo, cell_status);
     if (threadIdx.x != 0) return;
     const double R = clip::half_side_box(bbox, box);
     while (todo) {
-        const uint32_t a = blockIdx.x * kWave + (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1ull;
+        const uint32_t a = redo_next(todo);
         cell_status[a] = (uint8_t)clip::cell_box_serial(points, num_points, adj, offsets, num_edges, a, box, R, s_s, s_t,
                                                         kWaveCap, volume, centroid, nonempty, face_area, face_vertices,
                                                         wall_area, wall_vertices);
@@ -149,7 +123,7 @@ using namespace rf;
 
 extern "C" {
 
-size_t rf_cell_box_workspace_bytes(uint32_t num_points) { return ((size_t)num_points + 255u) & ~(size_t)255u; }
+size_t rf_cell_box_workspace_bytes(uint32_t num_points) { return redo_bytes(num_points); }
 
 int rf_cell_box(const float *points, uint32_t num_points, const uint32_t *point_adjacency,
                 const uint32_t *point_adjacency_offsets, uint32_t num_edges, const float *bbox, double lo_x, double lo_y,
@@ -161,21 +135,13 @@ int rf_cell_box(const float *points, uint32_t num_points, const uint32_t *point_
     if (!points || !point_adjacency_offsets || !bbox || !volume || !centroid || !nonempty || !wall_area ||
         !wall_vertices || !cell_status || (num_edges && (!point_adjacency || !face_area || !face_vertices)))
         return fail(RF_ERR_INVALID_ARGUMENT, "rf_cell_box: null pointer");
-    if (!(lo_x < hi_x && lo_y < hi_y && lo_z < hi_z) || !(hi_x - lo_x < __builtin_inf()) ||
-        !(hi_y - lo_y < __builtin_inf()) || !(hi_z - lo_z < __builtin_inf()))
-        return fail(RF_ERR_INVALID_ARGUMENT, "rf_cell_box: the box must be finite with lo < hi");
+    if (int rc = check_box("rf_cell_box", lo_x, lo_y, lo_z, hi_x, hi_y, hi_z)) return rc;
     if (!workspace || workspace_bytes < rf_cell_box_workspace_bytes(num_points))
         return fail(RF_ERR_WORKSPACE, "rf_cell_box: workspace missing or too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *redo = static_cast<uint8_t *>(workspace);
-    hipLaunchKernelGGL(cell_box::cell_box_kernel, dim3(num_points), dim3(cell_box::kWave), 0, s, points, num_points,
-                       point_adjacency, point_adjacency_offsets, num_edges, bbox, lo_x, lo_y, lo_z, hi_x, hi_y, hi_z, volume,
-                       centroid, nonempty, face_area, face_vertices, wall_area, wall_vertices, redo);
-    hipLaunchKernelGGL(cell_box::cell_box_redo_kernel, dim3((num_points + cell_box::kWave - 1u) / cell_box::kWave),
-                       dim3(cell_box::kWave), 0, s, points, num_points, point_adjacency, point_adjacency_offsets,
-                       num_edges, bbox, lo_x, lo_y, lo_z, hi_x, hi_y, hi_z, volume, centroid, nonempty, face_area,
-                       face_vertices, wall_area, wall_vertices, redo, cell_status);
-    return check_launch("rf_cell_box");
+    return launch_cell_waves("rf_cell_box", stream, num_points, workspace, cell_status, cell_box::cell_box_kernel,
+                             cell_box::cell_box_redo_kernel, points, num_points, point_adjacency,
+                             point_adjacency_offsets, num_edges, bbox, lo_x, lo_y, lo_z, hi_x, hi_y, hi_z, volume,
+                             centroid, nonempty, face_area, face_vertices, wall_area, wall_vertices);
 }
 
 }  // extern "C"

@@ -1,18 +1,15 @@
 // rf_cell_box_grad.hip -- point gradients of the volumes and centroids of the Voronoi cells clipped to an axis-aligned
 // box ("Point gradients of the cells in a box").  The mathematics: rf_clip_box_grad.hpp; the plane list and
-// its tie rule: rf_clip_box.hpp; the moments and the per-face arithmetic: rf_clip_grad.hpp, all in double.
+// its tie rule: rf_clip_box.hpp; the moments and the per-face arithmetic: rf_clip_grad.hpp, all in double.  The wave
+// scheme, its LDS layout and the hand-off through redo[cell]: rf_cell_wave.hpp.
 //
-//   cell_box_grad_kernel       one wave per cell, one lane per ROW face, the layout of cell_geometry_grad_kernel and
-//                              cell_box_kernel: the list's planes {d, h} staged once in LDS (the row's by their lanes, the
-//                              six walls behind them by lanes 0..5), each lane's polygon in its vertex-major LDS slot (no
-//                              per-lane arrays).  The lane clips its face again by the whole list in list order, takes the
-//                              polygon's moments, reads its neighbour's gV, gC, V, c and nonempty and forms its 3-vector;
-//                              three __shfl_xor reductions, and lane 0 writes the row.  A face with an empty cell on
-//                              either side is passed over.  The walls do not move: they are clip planes only and take
-//                              no lanes, so rows of up to 64 faces (lists of up to 70 planes) stay here.  Longer rows
-//                              and polygons of more than kLaneCap vertices are handed on, unwritten, through redo[cell].
-//   cell_box_grad_redo_kernel  one wave per 64 cells: the cells handed on are walked by lane 0, face after face
-//                              (rf::clip::cell_box_grad_serial, what the host harness runs), with kWaveCap vertices.
+//   cell_box_grad_kernel       one lane per ROW face; the six walls are staged behind the row by lanes 0..5.  The lane
+//                              clips its face again by the whole list in list order, takes the polygon's moments, reads
+//                              its neighbour's gV, gC, V, c and nonempty and forms its 3-vector; three wave sums, and
+//                              lane 0 writes the row.  A face with an empty cell on either side is passed over.  The
+//                              walls do not move: they are clip planes only and take no lanes, so rows of up to 64 faces
+//                              (lists of up to 70 planes) stay here.
+//   cell_box_grad_redo_kernel  the cells handed on, by rf::clip::cell_box_grad_serial.
 //
 // Row a is a gather over a's own adjacency row: every output element is written exactly once by a plain store, there are
 // no atomics, and the result is bit-reproducible.
@@ -21,21 +18,11 @@
 #include <stdint.h>
 
 #include "../../include/radfoam_hip_box_grad.h"
+#include "rf_cell_wave.hpp"
 #include "rf_clip_box_grad.hpp"
-#include "rf_host.hpp"
 
 namespace rf {
 namespace cell_box_grad {
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kLaneCap = 16;    // as cell_box_kernel: 32 KiB of polygons per wave
-constexpr uint32_t kWaveCap = 256;   // as cell_box_redo_kernel
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(64) void cell_box_grad_kernel(
     const float *__restrict__ points, uint32_t num_points, const uint32_t *__restrict__ adj,
@@ -49,48 +36,30 @@ __global__ __launch_bounds__(64) void cell_box_grad_kernel(
     const clip::Box box = {lo_x, lo_y, lo_z, hi_x, hi_y, hi_z};
     const uint32_t a = blockIdx.x, lane = threadIdx.x;
     const uint32_t begin = offsets[a], end = offsets[a + 1];
-    if (begin > end || end > num_edges || end - begin > kWave) {   // wave-uniform
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (begin > end || end > num_edges || end - begin > kWave) return hand_on(redo, a, lane);   // wave-uniform
     const uint32_t degree = end - begin, count = degree + clip::kWalls;
     if (degree == 0) {   // no neighbours: the cell is the whole box wherever the site is
         if (lane == 0) {
             grad_points[3 * (size_t)a] = grad_points[3 * (size_t)a + 1] = grad_points[3 * (size_t)a + 2] = 0.0;
-            redo[a] = 0;
+            keep(redo, a);
         }
         return;
     }
-    const bool have = lane < degree;
-    uint32_t q = have ? adj[begin + lane] : 0u;
-    bool bad = have && (q >= num_points || q == a);
-    if (!have || bad) q = a;
-    double dx, dy, dz, h;
-    clip::neighbour(points, a, q, dx, dy, dz, h);
-    bad = bad || (have && !(h > 0.0));
-    if (have) s_plane[0][lane] = dx, s_plane[1][lane] = dy, s_plane[2][lane] = dz, s_plane[3][lane] = h;
-    if (lane < clip::kWalls) {
-        double wx, wy, wz, wh;
-        clip::wall_plane(points, a, box, lane, wx, wy, wz, wh);
-        s_plane[0][degree + lane] = wx, s_plane[1][degree + lane] = wy, s_plane[2][degree + lane] = wz;
-        s_plane[3][degree + lane] = wh;
-    }
-    __syncthreads();
-    if (__any(bad)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    const CellLane f = load_neighbour(points, num_points, adj, a, begin, degree, lane);
+    if (f.have) store_plane(s_plane, lane, f.dx, f.dy, f.dz, f.h);
+    stage_walls(points, a, box, degree, lane, s_plane);
+    if (sync_any_bad(f.bad)) return hand_on(redo, a, lane);
     const double R = clip::half_side_box(bbox, box);
     bool overflow = false;
     double gx = 0.0, gy = 0.0, gz = 0.0;
-    if (have && nonempty[a] && nonempty[q]) {   // a face with an empty cell on either side carries no term
-        const clip::Frame frame = clip::list_frame(false, dx, dy, dz, h);
+    if (f.have && nonempty[a] && nonempty[f.q]) {   // a face with an empty cell on either side carries no term
+        const clip::Frame frame = clip::list_frame(false, f.dx, f.dy, f.dz, f.h);
         double *s = &s_s[0][lane], *t = &s_t[0][lane];
         clip::init_square(s, t, kWave, R);
         uint32_t m = 4, cur = 0;
-        for (uint32_t j = 0; j < count && m != 0; ++j) {
+        for (uint32_t j = 0; j < count && m != 0; ++j) {   // by the other planes of the list, in list order
             if (j == lane) continue;
-            if (!clip::clip_by_list_plane(frame, dx, dy, dz, j < lane, s_plane[0][j], s_plane[1][j], s_plane[2][j],
+            if (!clip::clip_by_list_plane(frame, f.dx, f.dy, f.dz, j < lane, s_plane[0][j], s_plane[1][j], s_plane[2][j],
                                           s_plane[3][j], s, t, kWave, kLaneCap, m, cur)) {
                 overflow = true;
                 break;
@@ -100,19 +69,16 @@ __global__ __launch_bounds__(64) void cell_box_grad_kernel(
             const clip::Moments mo = clip::moments(s + cur * kLaneCap * kWave, t + cur * kLaneCap * kWave, kWave, m, R);
             const clip::CellTerm ca = clip::cell_term(points, a, a, volume, centroid, nonempty, grad_volume,
                                                       grad_centroid);
-            const clip::CellTerm cb = clip::cell_term(points, a, q, volume, centroid, nonempty, grad_volume,
+            const clip::CellTerm cb = clip::cell_term(points, a, f.q, volume, centroid, nonempty, grad_volume,
                                                       grad_centroid);
             clip::add_face_grad(frame, mo, ca, cb, gx, gy, gz);
         }
     }
-    if (__any(overflow)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (__any(overflow)) return hand_on(redo, a, lane);
     gx = wave_sum(gx), gy = wave_sum(gy), gz = wave_sum(gz);
     if (lane == 0) {
         grad_points[3 * (size_t)a] = gx, grad_points[3 * (size_t)a + 1] = gy, grad_points[3 * (size_t)a + 2] = gz;
-        redo[a] = 0;
+        keep(redo, a);
     }
 }
 
@@ -125,15 +91,11 @@ __global__ __launch_bounds__(64) void cell_box_grad_redo_kernel(
     uint8_t *__restrict__ cell_status) {
     __shared__ double s_s[2 * kWaveCap], s_t[2 * kWaveCap];
     const clip::Box box = {lo_x, lo_y, lo_z, hi_x, hi_y, hi_z};
-    const uint32_t cell = blockIdx.x * kWave + threadIdx.x;
-    const bool mine = cell < num_points && redo[cell] != 0;
-    if (cell < num_points && !mine) cell_status[cell] = (uint8_t)clip::kCellOk;
-    unsigned long long todo = __ballot(mine);
+    unsigned long long todo = redo_todo(num_points, redo, cell_status);
     if (threadIdx.x != 0) return;
     const double R = clip::half_side_box(bbox, box);
     while (todo) {
-        const uint32_t a = blockIdx.x * kWave + (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1ull;
+        const uint32_t a = redo_next(todo);
         cell_status[a] = (uint8_t)clip::cell_box_grad_serial(points, num_points, adj, offsets, num_edges, a, box, R, s_s,
                                                              s_t, kWaveCap, volume, centroid, nonempty, grad_volume,
                                                              grad_centroid, grad_points);
@@ -147,7 +109,7 @@ using namespace rf;
 
 extern "C" {
 
-size_t rf_cell_box_grad_workspace_bytes(uint32_t num_points) { return ((size_t)num_points + 255u) & ~(size_t)255u; }
+size_t rf_cell_box_grad_workspace_bytes(uint32_t num_points) { return redo_bytes(num_points); }
 
 int rf_cell_box_grad(const float *points, uint32_t num_points, const uint32_t *point_adjacency,
                      const uint32_t *point_adjacency_offsets, uint32_t num_edges, const float *bbox, double lo_x,
@@ -160,22 +122,13 @@ int rf_cell_box_grad(const float *points, uint32_t num_points, const uint32_t *p
     if (!points || !point_adjacency_offsets || !bbox || !volume || !centroid || !nonempty || !grad_points ||
         !cell_status || (num_edges && !point_adjacency))
         return fail(RF_ERR_INVALID_ARGUMENT, "rf_cell_box_grad: null pointer");
-    if (!(lo_x < hi_x && lo_y < hi_y && lo_z < hi_z) || !(hi_x - lo_x < __builtin_inf()) ||
-        !(hi_y - lo_y < __builtin_inf()) || !(hi_z - lo_z < __builtin_inf()))
-        return fail(RF_ERR_INVALID_ARGUMENT, "rf_cell_box_grad: the box must be finite with lo < hi");
+    if (int rc = check_box("rf_cell_box_grad", lo_x, lo_y, lo_z, hi_x, hi_y, hi_z)) return rc;
     if (!workspace || workspace_bytes < rf_cell_box_grad_workspace_bytes(num_points))
         return fail(RF_ERR_WORKSPACE, "rf_cell_box_grad: workspace missing or too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *redo = static_cast<uint8_t *>(workspace);
-    hipLaunchKernelGGL(cell_box_grad::cell_box_grad_kernel, dim3(num_points), dim3(cell_box_grad::kWave), 0, s, points,
-                       num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, lo_x, lo_y, lo_z, hi_x, hi_y,
-                       hi_z, volume, centroid, nonempty, grad_volume, grad_centroid, grad_points, redo);
-    hipLaunchKernelGGL(cell_box_grad::cell_box_grad_redo_kernel,
-                       dim3((num_points + cell_box_grad::kWave - 1u) / cell_box_grad::kWave), dim3(cell_box_grad::kWave),
-                       0, s, points, num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, lo_x, lo_y,
-                       lo_z, hi_x, hi_y, hi_z, volume, centroid, nonempty, grad_volume, grad_centroid, grad_points, redo,
-                       cell_status);
-    return check_launch("rf_cell_box_grad");
+    return launch_cell_waves("rf_cell_box_grad", stream, num_points, workspace, cell_status,
+                             cell_box_grad::cell_box_grad_kernel, cell_box_grad::cell_box_grad_redo_kernel, points,
+                             num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, lo_x, lo_y, lo_z,
+                             hi_x, hi_y, hi_z, volume, centroid, nonempty, grad_volume, grad_centroid, grad_points);
 }
 
 }  // extern "C"

@@ -1,20 +1,15 @@
 // rf_cell_box_moments.hip -- the second moments of the Voronoi cells clipped to an axis-aligned box: int y y^T dy about
 // the site and about the centroid ("Second moments of the cells clipped to a box").  The definition, the signed
 // pyramids and the closed form of the whole box: rf_clip_box_moments.hpp; the plane list, the wall frames and the tie rule
-// of coincident planes: rf_clip_box.hpp, all in double.
+// of coincident planes: rf_clip_box.hpp, all in double.  The wave scheme, its LDS layout and the hand-off through
+// redo[cell]: rf_cell_wave.hpp.
 //
-//   cell_box_moments_kernel       one wave per cell, one lane per plane of the cell's list, the layout of cell_box_kernel:
-//                                 the row's lanes first, then six wall lanes.  The list's planes {d, h} are staged once in
-//                                 LDS; each lane clips its face's square by the other planes in list order (the forward
-//                                 keeps no moments: the faces are clipped again), its polygon in an LDS slot (vertex-major,
-//                                 lanes side by side; no per-lane arrays), forms the polygon's moments and weights them
-//                                 with the signed height of its plane; six __shfl_xor reductions, and lane 0 forms the
-//                                 central moment and writes the twelve numbers.  Takes lists of up to 64 planes (rows of up
-//                                 to 58) whose polygons stay within kLaneCap vertices; anything else it hands on, untouched,
-//                                 through redo[cell].
-//   cell_box_moments_redo_kernel  one wave per 64 cells: the cells handed on are walked by lane 0, face after face
-//                                 (rf::clip::cell_box_moments_serial, what the host harness runs), with kWaveCap vertices.
-//                                 Beyond that the cell's status says so and the caller raises.
+//   cell_box_moments_kernel       one lane per plane of the cell's list, as cell_box_kernel: the row's lanes first, then
+//                                 six wall lanes.  The lane clips its face again (the forward keeps no moments), forms
+//                                 the polygon's moments and weights them with the signed height of its plane; six wave
+//                                 sums, and lane 0 forms the central moment and writes the twelve numbers.  Lists of up to
+//                                 64 planes (rows of up to 58).
+//   cell_box_moments_redo_kernel  the cells handed on, by rf::clip::cell_box_moments_serial.
 //
 // Cell a is a gather over a's own list: every output element is written exactly once by a plain store, there are no
 // atomics, and the result is bit-reproducible.
@@ -23,21 +18,11 @@
 #include <stdint.h>
 
 #include "../../include/radfoam_hip_box_moments.h"
+#include "rf_cell_wave.hpp"
 #include "rf_clip_box_moments.hpp"
-#include "rf_host.hpp"
 
 namespace rf {
 namespace cell_box_moments {
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kLaneCap = 16;    // as cell_box_kernel: 32 KiB of polygons per wave
-constexpr uint32_t kWaveCap = 256;   // as cell_box_redo_kernel
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(64) void cell_box_moments_kernel(
     const float *__restrict__ points, uint32_t num_points, const uint32_t *__restrict__ adj,
@@ -51,18 +36,18 @@ __global__ __launch_bounds__(64) void cell_box_moments_kernel(
     const clip::Box box = {lo_x, lo_y, lo_z, hi_x, hi_y, hi_z};
     const uint32_t a = blockIdx.x, lane = threadIdx.x;
     const uint32_t begin = offsets[a], end = offsets[a + 1];
-    if (begin > end || end > num_edges || end - begin > kWave - clip::kWalls) {   // wave-uniform
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (begin > end || end > num_edges || end - begin > kWave - clip::kWalls)   // wave-uniform
+        return hand_on(redo, a, lane);
     const uint32_t degree = end - begin, count = degree + clip::kWalls;
     if (degree == 0) {   // no neighbours: the whole box, in closed form
         if (lane == 0) {
             clip::whole_box_moments(points, a, box, site_moment, central_moment);
-            redo[a] = 0;
+            keep(redo, a);
         }
         return;
     }
+    // the staging with the walls as lanes, spelled out as in cell_box_kernel.  The load and the bad test are
+    // load_neighbour's of rf_cell_wave.hpp, line for line: keep the two in step.
     const bool row = lane < degree, wall = !row && lane < count;
     uint32_t q = row ? adj[begin + lane] : 0u;
     bool bad = row && (q >= num_points || q == a);
@@ -72,11 +57,7 @@ __global__ __launch_bounds__(64) void cell_box_moments_kernel(
     bad = bad || (row && !(h > 0.0));
     if (wall) clip::wall_plane(points, a, box, lane - degree, dx, dy, dz, h);   // a choice among values, not members
     s_plane[0][lane] = dx, s_plane[1][lane] = dy, s_plane[2][lane] = dz, s_plane[3][lane] = h;
-    __syncthreads();
-    if (__any(bad)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (sync_any_bad(bad)) return hand_on(redo, a, lane);
     const double R = clip::half_side_box(bbox, box);
     bool overflow = false;
     clip::MomentSums sums = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, false};
@@ -85,7 +66,7 @@ __global__ __launch_bounds__(64) void cell_box_moments_kernel(
         double *s = &s_s[0][lane], *t = &s_t[0][lane];
         clip::init_square(s, t, kWave, R);
         uint32_t m = 4, cur = 0;
-        for (uint32_t j = 0; j < count && m != 0; ++j) {
+        for (uint32_t j = 0; j < count && m != 0; ++j) {   // by the other planes of the list, in list order
             if (j == lane) continue;
             if (!clip::clip_by_list_plane(frame, dx, dy, dz, j < lane, s_plane[0][j], s_plane[1][j], s_plane[2][j],
                                           s_plane[3][j], s, t, kWave, kLaneCap, m, cur)) {
@@ -97,16 +78,13 @@ __global__ __launch_bounds__(64) void cell_box_moments_kernel(
             clip::add_face_moment_box(sums, frame, wall, h,
                                       clip::moments(s + cur * kLaneCap * kWave, t + cur * kLaneCap * kWave, kWave, m, R));
     }
-    if (__any(overflow)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (__any(overflow)) return hand_on(redo, a, lane);
     sums.unbounded = __any(sums.unbounded);   // cannot be: the walls are in the list; NaN rather than wrong
     sums.xx = wave_sum(sums.xx), sums.yy = wave_sum(sums.yy), sums.zz = wave_sum(sums.zz);
     sums.xy = wave_sum(sums.xy), sums.xz = wave_sum(sums.xz), sums.yz = wave_sum(sums.yz);
     if (lane == 0) {
         clip::write_moments_box(points, a, sums, volume, centroid, nonempty, site_moment, central_moment);
-        redo[a] = 0;
+        keep(redo, a);
     }
 }
 
@@ -118,15 +96,11 @@ __global__ __launch_bounds__(64) void cell_box_moments_redo_kernel(
     double *__restrict__ central_moment, const uint8_t *__restrict__ redo, uint8_t *__restrict__ cell_status) {
     __shared__ double s_s[2 * kWaveCap], s_t[2 * kWaveCap];
     const clip::Box box = {lo_x, lo_y, lo_z, hi_x, hi_y, hi_z};
-    const uint32_t cell = blockIdx.x * kWave + threadIdx.x;
-    const bool mine = cell < num_points && redo[cell] != 0;
-    if (cell < num_points && !mine) cell_status[cell] = (uint8_t)clip::kCellOk;
-    unsigned long long todo = __ballot(mine);
+    unsigned long long todo = redo_todo(num_points, redo, cell_status);
     if (threadIdx.x != 0) return;
     const double R = clip::half_side_box(bbox, box);
     while (todo) {
-        const uint32_t a = blockIdx.x * kWave + (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1ull;
+        const uint32_t a = redo_next(todo);
         cell_status[a] = (uint8_t)clip::cell_box_moments_serial(points, num_points, adj, offsets, num_edges, a, box, R, s_s,
                                                                 s_t, kWaveCap, volume, centroid, nonempty, site_moment,
                                                                 central_moment);
@@ -140,7 +114,7 @@ using namespace rf;
 
 extern "C" {
 
-size_t rf_cell_box_moments_workspace_bytes(uint32_t num_points) { return ((size_t)num_points + 255u) & ~(size_t)255u; }
+size_t rf_cell_box_moments_workspace_bytes(uint32_t num_points) { return redo_bytes(num_points); }
 
 int rf_cell_box_moments(const float *points, uint32_t num_points, const uint32_t *point_adjacency,
                         const uint32_t *point_adjacency_offsets, uint32_t num_edges, const float *bbox, double lo_x,
@@ -152,22 +126,13 @@ int rf_cell_box_moments(const float *points, uint32_t num_points, const uint32_t
     if (!points || !point_adjacency_offsets || !bbox || !volume || !centroid || !nonempty || !site_moment ||
         !central_moment || !cell_status || (num_edges && !point_adjacency))
         return fail(RF_ERR_INVALID_ARGUMENT, "rf_cell_box_moments: null pointer");
-    if (!(lo_x < hi_x && lo_y < hi_y && lo_z < hi_z) || !(hi_x - lo_x < __builtin_inf()) ||
-        !(hi_y - lo_y < __builtin_inf()) || !(hi_z - lo_z < __builtin_inf()))
-        return fail(RF_ERR_INVALID_ARGUMENT, "rf_cell_box_moments: the box must be finite with lo < hi");
+    if (int rc = check_box("rf_cell_box_moments", lo_x, lo_y, lo_z, hi_x, hi_y, hi_z)) return rc;
     if (!workspace || workspace_bytes < rf_cell_box_moments_workspace_bytes(num_points))
         return fail(RF_ERR_WORKSPACE, "rf_cell_box_moments: workspace missing or too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *redo = static_cast<uint8_t *>(workspace);
-    hipLaunchKernelGGL(cell_box_moments::cell_box_moments_kernel, dim3(num_points), dim3(cell_box_moments::kWave), 0, s,
-                       points, num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, lo_x, lo_y, lo_z,
-                       hi_x, hi_y, hi_z, volume, centroid, nonempty, site_moment, central_moment, redo);
-    hipLaunchKernelGGL(cell_box_moments::cell_box_moments_redo_kernel,
-                       dim3((num_points + cell_box_moments::kWave - 1u) / cell_box_moments::kWave),
-                       dim3(cell_box_moments::kWave), 0, s, points, num_points, point_adjacency, point_adjacency_offsets,
-                       num_edges, bbox, lo_x, lo_y, lo_z, hi_x, hi_y, hi_z, volume, centroid, nonempty, site_moment,
-                       central_moment, redo, cell_status);
-    return check_launch("rf_cell_box_moments");
+    return launch_cell_waves("rf_cell_box_moments", stream, num_points, workspace, cell_status,
+                             cell_box_moments::cell_box_moments_kernel, cell_box_moments::cell_box_moments_redo_kernel,
+                             points, num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, lo_x, lo_y,
+                             lo_z, hi_x, hi_y, hi_z, volume, centroid, nonempty, site_moment, central_moment);
 }
 
 }  // extern "C"

@@ -1,15 +1,11 @@
 // rf_cell_geometry.hip -- what a Voronoi cell IS: volume, centroid, boundedness, face areas, and the faces between
 // selected and unselected cells as triangles ("Cell geometry").  Clipping core: rf_clip.hpp, all in double.
+// The wave scheme, its LDS layout and the hand-off through redo[cell]: rf_cell_wave.hpp.
 //
-//   cell_geometry_kernel       one wave per cell, one lane per face.  The row's planes {d_c, |d_c|^2/2} are staged once
-//                              in LDS; each lane clips its face's square by the other planes, its polygon in an LDS slot
-//                              (vertex-major, lanes side by side: lanes at the same vertex index hit different banks).
-//                              Volume and centroid are wave reductions.  Takes rows of up to 64 faces whose polygons stay
-//                              within kLaneCap vertices; anything else it hands on, untouched, through redo[cell].
-//   cell_geometry_redo_kernel  one wave per 64 cells: a lane per cell reads redo[cell]; the cells handed on are walked one
-//                              after the other, face by face, by lane 0 (rf::clip::cell_serial, what the host harness
-//                              runs) with room for kWaveCap vertices: slow, and rare -- rows longer than 64, faces like
-//                              the 48-gon of the tests.  Beyond that the cell's status says so and the caller raises.
+//   cell_geometry_kernel       the scheme's plain form: the face's area and vertex count per lane, volume and first
+//                              moments as wave reductions.  Rows of up to 64 faces.
+//   cell_geometry_redo_kernel  the cells handed on, by rf::clip::cell_serial: rows longer than 64, faces like the 48-gon
+//                              of the tests.
 //   surface_count_kernel       lane per adjacency slot: triangles of the face if it separates inside from outside.
 //   surface_emit_kernel        wave per listed slot: lane 0 clips the face, the wave writes its triangle fan.
 //
@@ -19,20 +15,9 @@
 #include <stdint.h>
 
 #include "../../include/radfoam_hip_geometry.h"
-#include "rf_clip.hpp"
-#include "rf_host.hpp"
+#include "rf_cell_wave.hpp"
 
 namespace rf {
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kLaneCap = 16;    // polygon vertices per lane: 2 buffers * 2 coordinates * 16 * 64 lanes * 8 B = 32 KiB
-constexpr uint32_t kWaveCap = 256;   // polygon vertices of the serial path: 8 KiB
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(64) void cell_geometry_kernel(
     const float *__restrict__ points, uint32_t num_points, const uint32_t *__restrict__ adj,
@@ -44,67 +29,39 @@ __global__ __launch_bounds__(64) void cell_geometry_kernel(
     __shared__ double s_t[2 * kLaneCap][kWave];
     const uint32_t a = blockIdx.x, lane = threadIdx.x;
     const uint32_t begin = offsets[a], end = offsets[a + 1];
-    if (begin > end || end > num_edges || end - begin > kWave) {   // wave-uniform
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (begin > end || end > num_edges || end - begin > kWave) return hand_on(redo, a, lane);   // wave-uniform
     const uint32_t degree = end - begin;
     if (degree == 0) {   // no neighbours: the whole space
         if (lane == 0) {
             volume[a] = __builtin_inf();
             centroid[3 * (size_t)a] = centroid[3 * (size_t)a + 1] = centroid[3 * (size_t)a + 2] = __builtin_nan("");
             bounded[a] = 0;
-            redo[a] = 0;
+            keep(redo, a);
         }
         return;
     }
-    const bool have = lane < degree;
-    uint32_t q = have ? adj[begin + lane] : 0u;
-    bool bad = have && (q >= num_points || q == a);
-    if (!have || bad) q = a;
-    double dx, dy, dz, h;
-    clip::neighbour(points, a, q, dx, dy, dz, h);
-    bad = bad || (have && !(h > 0.0));
-    s_plane[0][lane] = dx, s_plane[1][lane] = dy, s_plane[2][lane] = dz, s_plane[3][lane] = h;
-    __syncthreads();
-    if (__any(bad)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    const CellLane f = stage_row(points, num_points, adj, a, begin, degree, lane, s_plane);
+    if (sync_any_bad(f.bad)) return hand_on(redo, a, lane);
     const double R = clip::half_side(bbox);
     bool overflow = false, unbounded = false;
     double area = 0.0, vol = 0.0, mx = 0.0, my = 0.0, mz = 0.0;
     uint32_t m = 0;
-    if (have) {
-        const clip::Frame frame = clip::make_frame(dx, dy, dz);
+    if (f.have) {
+        const clip::Frame frame = clip::make_frame(f.dx, f.dy, f.dz);
         double *s = &s_s[0][lane], *t = &s_t[0][lane];
-        clip::init_square(s, t, kWave, R);
-        m = 4;
-        uint32_t cur = 0;
-        for (uint32_t j = 0; j < degree && m != 0; ++j) {
-            if (j == lane) continue;
-            double A, B, C;
-            clip::plane_in_frame(frame, s_plane[0][j], s_plane[1][j], s_plane[2][j], s_plane[3][j], A, B, C);
-            const uint32_t in = cur * kLaneCap * kWave, out = (cur ^ 1u) * kLaneCap * kWave;
-            if (!clip::clip_step(s + in, t + in, s + out, t + out, kWave, kLaneCap, m, A, B, C)) {
-                overflow = true;
-                break;
-            }
-            cur ^= 1u;
-        }
+        const Clipped c = clip_by_row(frame, s_plane, degree, lane, R, s, t);
+        m = c.m, overflow = c.overflow;
         if (!overflow) {
+            const uint32_t at = c.cur * kLaneCap * kWave;
             double cs, ct;
-            clip::measure(s + cur * kLaneCap * kWave, t + cur * kLaneCap * kWave, kWave, m, R, area, cs, ct, unbounded);
+            clip::measure(s + at, t + at, kWave, m, R, area, cs, ct, unbounded);
             clip::CellSums sums = {0.0, 0.0, 0.0, 0.0, false};
             clip::add_face(sums, frame, area, cs, ct, unbounded);
             vol = sums.volume, mx = sums.mx, my = sums.my, mz = sums.mz;
         }
     }
-    if (__any(overflow)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
-    if (have) {
+    if (__any(overflow)) return hand_on(redo, a, lane);
+    if (f.have) {
         face_area[begin + lane] = unbounded ? __builtin_inf() : area;
         face_vertices[begin + lane] = m;
     }
@@ -117,7 +74,7 @@ __global__ __launch_bounds__(64) void cell_geometry_kernel(
         centroid[3 * (size_t)a + 1] = open ? __builtin_nan("") : (double)p[1] + my / vol;
         centroid[3 * (size_t)a + 2] = open ? __builtin_nan("") : (double)p[2] + mz / vol;
         bounded[a] = open ? 0 : 1;
-        redo[a] = 0;
+        keep(redo, a);
     }
 }
 
@@ -128,15 +85,11 @@ __global__ __launch_bounds__(64) void cell_geometry_redo_kernel(
     double *__restrict__ face_area, uint32_t *__restrict__ face_vertices, const uint8_t *__restrict__ redo,
     uint8_t *__restrict__ cell_status) {
     __shared__ double s_s[2 * kWaveCap], s_t[2 * kWaveCap];
-    const uint32_t cell = blockIdx.x * kWave + threadIdx.x;
-    const bool mine = cell < num_points && redo[cell] != 0;
-    if (cell < num_points && !mine) cell_status[cell] = (uint8_t)clip::kCellOk;
-    unsigned long long todo = __ballot(mine);
+    unsigned long long todo = redo_todo(num_points, redo, cell_status);
     if (threadIdx.x != 0) return;
     const double R = clip::half_side(bbox);
     while (todo) {
-        const uint32_t a = blockIdx.x * kWave + (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1ull;
+        const uint32_t a = redo_next(todo);
         cell_status[a] = (uint8_t)clip::cell_serial(points, num_points, adj, offsets, num_edges, a, R, s_s, s_t, kWaveCap,
                                                     volume, centroid, bounded, face_area, face_vertices);
     }
@@ -229,7 +182,7 @@ using namespace rf;
 
 extern "C" {
 
-size_t rf_cell_geometry_workspace_bytes(uint32_t num_points) { return ((size_t)num_points + 255u) & ~(size_t)255u; }
+size_t rf_cell_geometry_workspace_bytes(uint32_t num_points) { return redo_bytes(num_points); }
 
 int rf_cell_geometry(const float *points, uint32_t num_points, const uint32_t *point_adjacency,
                      const uint32_t *point_adjacency_offsets, uint32_t num_edges, const float *bbox, double *volume,
@@ -242,15 +195,9 @@ int rf_cell_geometry(const float *points, uint32_t num_points, const uint32_t *p
         return fail(RF_ERR_INVALID_ARGUMENT, "rf_cell_geometry: null pointer");
     if (!workspace || workspace_bytes < rf_cell_geometry_workspace_bytes(num_points))
         return fail(RF_ERR_WORKSPACE, "rf_cell_geometry: workspace missing or too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *redo = static_cast<uint8_t *>(workspace);
-    hipLaunchKernelGGL(cell_geometry_kernel, dim3(num_points), dim3(kWave), 0, s, points, num_points, point_adjacency,
-                       point_adjacency_offsets, num_edges, bbox, volume, centroid, bounded, face_area, face_vertices,
-                       redo);
-    hipLaunchKernelGGL(cell_geometry_redo_kernel, dim3((num_points + kWave - 1u) / kWave), dim3(kWave), 0, s, points, num_points,
-                       point_adjacency, point_adjacency_offsets, num_edges, bbox, volume, centroid, bounded, face_area,
-                       face_vertices, redo, cell_status);
-    return check_launch("rf_cell_geometry");
+    return launch_cell_waves("rf_cell_geometry", stream, num_points, workspace, cell_status, cell_geometry_kernel,
+                             cell_geometry_redo_kernel, points, num_points, point_adjacency, point_adjacency_offsets,
+                             num_edges, bbox, volume, centroid, bounded, face_area, face_vertices);
 }
 
 int rf_cell_surface_count(uint32_t num_points, const uint32_t *point_adjacency,

@@ -1,15 +1,11 @@
 // rf_cell_geometry_grad.hip -- point gradients of the cells' volumes and centroids ("Point gradients of the
-// cell geometry").  The mathematics and the per-face arithmetic: rf_clip_grad.hpp, all in double.
+// cell geometry").  The mathematics and the per-face arithmetic: rf_clip_grad.hpp, all in double.  The wave scheme, its
+// LDS layout and the hand-off through redo[cell]: rf_cell_wave.hpp.
 //
-//   cell_geometry_grad_kernel       one wave per cell, one lane per face, the layout of cell_geometry_kernel: the row's
-//                                   planes staged in LDS, each lane's polygon in its vertex-major LDS slot (no per-lane
-//                                   arrays).  The lane clips its face again (the forward keeps no moments: 48 B a face),
-//                                   takes the polygon's moments, reads its neighbour's gV, gC, V, c and bounded and
-//                                   forms its 3-vector; a __shfl_xor reduction, and lane 0 writes the row.  Rows of more
-//                                   than 64 faces and polygons of more than kLaneCap vertices are handed on, unwritten,
-//                                   through redo[cell].
-//   cell_geometry_grad_redo_kernel  one wave per 64 cells: the cells handed on are walked by lane 0, face after face
-//                                   (rf::clip::cell_grad_serial, what the host harness runs), with kWaveCap vertices.
+//   cell_geometry_grad_kernel       the lane clips its face again (the forward keeps no moments: 48 B a face), takes the
+//                                   polygon's moments, reads its neighbour's gV, gC, V, c and bounded and forms its
+//                                   3-vector; three wave sums, and lane 0 writes the row.  Rows of up to 64 faces.
+//   cell_geometry_grad_redo_kernel  the cells handed on, by rf::clip::cell_grad_serial.
 //
 // Row a is a gather over a's own adjacency row: every output element is written exactly once by a plain store, there are
 // no atomics, and the result is bit-reproducible.
@@ -18,21 +14,11 @@
 #include <stdint.h>
 
 #include "../../include/radfoam_hip_geometry_grad.h"
+#include "rf_cell_wave.hpp"
 #include "rf_clip_grad.hpp"
-#include "rf_host.hpp"
 
 namespace rf {
 namespace geometry_grad {
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kLaneCap = 16;    // as cell_geometry_kernel: 32 KiB of polygons per wave
-constexpr uint32_t kWaveCap = 256;   // as cell_geometry_redo_kernel
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(64) void cell_geometry_grad_kernel(
     const float *__restrict__ points, uint32_t num_points, const uint32_t *__restrict__ adj,
@@ -45,69 +31,42 @@ __global__ __launch_bounds__(64) void cell_geometry_grad_kernel(
     __shared__ double s_t[2 * kLaneCap][kWave];
     const uint32_t a = blockIdx.x, lane = threadIdx.x;
     const uint32_t begin = offsets[a], end = offsets[a + 1];
-    if (begin > end || end > num_edges || end - begin > kWave) {   // wave-uniform
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (begin > end || end > num_edges || end - begin > kWave) return hand_on(redo, a, lane);   // wave-uniform
     const uint32_t degree = end - begin;
     if (degree == 0) {   // no neighbours: nothing depends on this site through its own row
         if (lane == 0) {
             grad_points[3 * (size_t)a] = grad_points[3 * (size_t)a + 1] = grad_points[3 * (size_t)a + 2] = 0.0;
-            redo[a] = 0;
+            keep(redo, a);
         }
         return;
     }
-    const bool have = lane < degree;
-    uint32_t q = have ? adj[begin + lane] : 0u;
-    bool bad = have && (q >= num_points || q == a);
-    if (!have || bad) q = a;
-    double dx, dy, dz, h;
-    clip::neighbour(points, a, q, dx, dy, dz, h);
-    bad = bad || (have && !(h > 0.0));
-    s_plane[0][lane] = dx, s_plane[1][lane] = dy, s_plane[2][lane] = dz, s_plane[3][lane] = h;
-    __syncthreads();
-    if (__any(bad)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    const CellLane f = stage_row(points, num_points, adj, a, begin, degree, lane, s_plane);
+    if (sync_any_bad(f.bad)) return hand_on(redo, a, lane);
     const double R = clip::half_side(bbox);
     bool overflow = false;
     double gx = 0.0, gy = 0.0, gz = 0.0;
-    if (have) {
-        const clip::Frame frame = clip::make_frame(dx, dy, dz);
+    if (f.have) {
+        const clip::Frame frame = clip::make_frame(f.dx, f.dy, f.dz);
         double *s = &s_s[0][lane], *t = &s_t[0][lane];
-        clip::init_square(s, t, kWave, R);
-        uint32_t m = 4, cur = 0;
-        for (uint32_t j = 0; j < degree && m != 0; ++j) {
-            if (j == lane) continue;
-            double A, B, C;
-            clip::plane_in_frame(frame, s_plane[0][j], s_plane[1][j], s_plane[2][j], s_plane[3][j], A, B, C);
-            const uint32_t in = cur * kLaneCap * kWave, out = (cur ^ 1u) * kLaneCap * kWave;
-            if (!clip::clip_step(s + in, t + in, s + out, t + out, kWave, kLaneCap, m, A, B, C)) {
-                overflow = true;
-                break;
-            }
-            cur ^= 1u;
-        }
+        const Clipped c = clip_by_row(frame, s_plane, degree, lane, R, s, t);
+        overflow = c.overflow;
         if (!overflow) {
-            const clip::Moments mo = clip::moments(s + cur * kLaneCap * kWave, t + cur * kLaneCap * kWave, kWave, m, R);
+            const uint32_t at = c.cur * kLaneCap * kWave;
+            const clip::Moments mo = clip::moments(s + at, t + at, kWave, c.m, R);
             if (!mo.unbounded) {   // q < num_points: no lane of this wave is bad
                 const clip::CellTerm ca = clip::cell_term(points, a, a, volume, centroid, bounded, grad_volume,
                                                           grad_centroid);
-                const clip::CellTerm cb = clip::cell_term(points, a, q, volume, centroid, bounded, grad_volume,
+                const clip::CellTerm cb = clip::cell_term(points, a, f.q, volume, centroid, bounded, grad_volume,
                                                           grad_centroid);
                 clip::add_face_grad(frame, mo, ca, cb, gx, gy, gz);
             }
         }
     }
-    if (__any(overflow)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (__any(overflow)) return hand_on(redo, a, lane);
     gx = wave_sum(gx), gy = wave_sum(gy), gz = wave_sum(gz);
     if (lane == 0) {
         grad_points[3 * (size_t)a] = gx, grad_points[3 * (size_t)a + 1] = gy, grad_points[3 * (size_t)a + 2] = gz;
-        redo[a] = 0;
+        keep(redo, a);
     }
 }
 
@@ -118,15 +77,11 @@ __global__ __launch_bounds__(64) void cell_geometry_grad_redo_kernel(
     const double *__restrict__ grad_volume, const double *__restrict__ grad_centroid,
     double *__restrict__ grad_points, const uint8_t *__restrict__ redo, uint8_t *__restrict__ cell_status) {
     __shared__ double s_s[2 * kWaveCap], s_t[2 * kWaveCap];
-    const uint32_t cell = blockIdx.x * kWave + threadIdx.x;
-    const bool mine = cell < num_points && redo[cell] != 0;
-    if (cell < num_points && !mine) cell_status[cell] = (uint8_t)clip::kCellOk;
-    unsigned long long todo = __ballot(mine);
+    unsigned long long todo = redo_todo(num_points, redo, cell_status);
     if (threadIdx.x != 0) return;
     const double R = clip::half_side(bbox);
     while (todo) {
-        const uint32_t a = blockIdx.x * kWave + (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1ull;
+        const uint32_t a = redo_next(todo);
         cell_status[a] = (uint8_t)clip::cell_grad_serial(points, num_points, adj, offsets, num_edges, a, R, s_s, s_t,
                                                          kWaveCap, volume, centroid, bounded, grad_volume,
                                                          grad_centroid, grad_points);
@@ -140,9 +95,7 @@ using namespace rf;
 
 extern "C" {
 
-size_t rf_cell_geometry_grad_workspace_bytes(uint32_t num_points) {
-    return ((size_t)num_points + 255u) & ~(size_t)255u;
-}
+size_t rf_cell_geometry_grad_workspace_bytes(uint32_t num_points) { return redo_bytes(num_points); }
 
 int rf_cell_geometry_grad(const float *points, uint32_t num_points, const uint32_t *point_adjacency,
                           const uint32_t *point_adjacency_offsets, uint32_t num_edges, const float *bbox,
@@ -156,17 +109,10 @@ int rf_cell_geometry_grad(const float *points, uint32_t num_points, const uint32
         return fail(RF_ERR_INVALID_ARGUMENT, "rf_cell_geometry_grad: null pointer");
     if (!workspace || workspace_bytes < rf_cell_geometry_grad_workspace_bytes(num_points))
         return fail(RF_ERR_WORKSPACE, "rf_cell_geometry_grad: workspace missing or too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *redo = static_cast<uint8_t *>(workspace);
-    hipLaunchKernelGGL(geometry_grad::cell_geometry_grad_kernel, dim3(num_points), dim3(geometry_grad::kWave), 0, s,
-                       points, num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, volume, centroid,
-                       bounded, grad_volume, grad_centroid, grad_points, redo);
-    hipLaunchKernelGGL(geometry_grad::cell_geometry_grad_redo_kernel,
-                       dim3((num_points + geometry_grad::kWave - 1u) / geometry_grad::kWave),
-                       dim3(geometry_grad::kWave), 0, s, points, num_points, point_adjacency, point_adjacency_offsets,
-                       num_edges, bbox, volume, centroid, bounded, grad_volume, grad_centroid, grad_points, redo,
-                       cell_status);
-    return check_launch("rf_cell_geometry_grad");
+    return launch_cell_waves("rf_cell_geometry_grad", stream, num_points, workspace, cell_status,
+                             geometry_grad::cell_geometry_grad_kernel, geometry_grad::cell_geometry_grad_redo_kernel,
+                             points, num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, volume,
+                             centroid, bounded, grad_volume, grad_centroid, grad_points);
 }
 
 }  // extern "C"

@@ -23,15 +23,13 @@
 #include <stdint.h>
 
 #include "../../include/radfoam_hip_mesh.h"
+#include "rf_cell_wave.hpp"
 #include "rf_clip_mesh.hpp"
-#include "rf_host.hpp"
 
 namespace rf {
 namespace cell_mesh {
 
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kLaneCap = 16;    // as cell_geometry_kernel: 32 KiB of polygons per wave, 4 KiB of labels
-constexpr uint32_t kWaveCap = 256;   // as cell_geometry_redo_kernel
+// kWave, kLaneCap, kWaveCap and the redo sweep: rf_cell_wave.hpp (here 32 KiB of polygons and 4 KiB of labels per wave)
 constexpr uint32_t kLongRow = 0xFFFFu;   // a uint16 label cannot name this row index apart from "none"
 constexpr uint32_t kFlat = 256;
 
@@ -94,15 +92,11 @@ __global__ __launch_bounds__(64) void mesh_emit_redo_kernel(
     uint32_t *__restrict__ corner_sites, const uint8_t *__restrict__ redo, uint8_t *__restrict__ face_status) {
     __shared__ double s_s[2 * kWaveCap], s_t[2 * kWaveCap];
     __shared__ uint32_t s_l[2 * kWaveCap];
-    const uint32_t face = blockIdx.x * kWave + threadIdx.x;
-    const bool mine = face < num_faces && redo[face] != 0;
-    if (face < num_faces && !mine) face_status[face] = (uint8_t)clip::kCellOk;
-    unsigned long long todo = __ballot(mine);
+    unsigned long long todo = redo_todo(num_faces, redo, face_status);
     if (threadIdx.x != 0) return;
     const double R = clip::half_side(bbox);
     while (todo) {
-        const uint32_t i = blockIdx.x * kWave + (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1ull;
+        const uint32_t i = redo_next(todo);
         uint32_t e = 0, a = clip::kNoSite, nv = 0;
         int64_t first = 0;
         uint32_t status = clip::kCellBadRow;
@@ -159,7 +153,7 @@ using namespace rf;
 
 extern "C" {
 
-size_t rf_cell_mesh_emit_workspace_bytes(uint32_t num_faces) { return ((size_t)num_faces + 255u) & ~(size_t)255u; }
+size_t rf_cell_mesh_emit_workspace_bytes(uint32_t num_faces) { return redo_bytes(num_faces); }
 
 int rf_cell_mesh_emit(const float *points, uint32_t num_points, const uint32_t *point_adjacency,
                       const uint32_t *point_adjacency_offsets, uint32_t num_edges, const float *bbox,
@@ -175,7 +169,7 @@ int rf_cell_mesh_emit(const float *points, uint32_t num_points, const uint32_t *
         return fail(RF_ERR_WORKSPACE, "rf_cell_mesh_emit: workspace missing or too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t *redo = static_cast<uint8_t *>(workspace);
-    const dim3 grid((num_faces + cell_mesh::kWave - 1u) / cell_mesh::kWave), block(cell_mesh::kWave);
+    const dim3 grid((num_faces + kWave - 1u) / kWave), block(kWave);
     hipLaunchKernelGGL(cell_mesh::mesh_emit_kernel, grid, block, 0, s, points, num_points, point_adjacency,
                        point_adjacency_offsets, num_edges, bbox, face_vertices, slots, corner_begin, num_faces, num_corners,
                        corner_xyz, corner_sites, redo);

@@ -1,16 +1,12 @@
 // rf_cell_moments.hip -- the second moments of the Voronoi cells: int y y^T dy about the site and about the centroid
 // ("Second moments of the cells").  The mathematics and the per-face arithmetic: rf_clip_moments.hpp, all in
-// double.
+// double.  The wave scheme, its LDS layout and the hand-off through redo[cell]: rf_cell_wave.hpp.
 //
-//   cell_moments_kernel       one wave per cell, one lane per face, the layout of cell_geometry_kernel: the row's planes
-//                             staged in LDS, each lane's polygon in its vertex-major LDS slot (no per-lane arrays).  The
-//                             lane clips its face again (the forward keeps no moments: 48 B a face), lifts the polygon's
-//                             moments into its pyramid's six sums; six __shfl_xor reductions, and lane 0 forms the central
+//   cell_moments_kernel       the lane clips its face again (the forward keeps no moments: 48 B a face) and lifts the
+//                             polygon's moments into its pyramid's six sums; six wave sums, and lane 0 forms the central
 //                             moment and writes the twelve numbers.  An unbounded cell is NaN before anything is clipped.
-//                             Rows of more than 64 faces and polygons of more than kLaneCap vertices are handed on,
-//                             unwritten, through redo[cell].
-//   cell_moments_redo_kernel  one wave per 64 cells: the cells handed on are walked by lane 0, face after face
-//                             (rf::clip::cell_moments_serial, what the host harness runs), with kWaveCap vertices.
+//                             Rows of up to 64 faces.
+//   cell_moments_redo_kernel  the cells handed on, by rf::clip::cell_moments_serial.
 //
 // Cell a is a gather over a's own adjacency row: every output element is written exactly once by a plain store, there are
 // no atomics, and the result is bit-reproducible.
@@ -19,21 +15,11 @@
 #include <stdint.h>
 
 #include "../../include/radfoam_hip_moments.h"
+#include "rf_cell_wave.hpp"
 #include "rf_clip_moments.hpp"
-#include "rf_host.hpp"
 
 namespace rf {
 namespace cell_moments {
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kLaneCap = 16;    // as cell_geometry_kernel: 32 KiB of polygons per wave
-constexpr uint32_t kWaveCap = 256;   // as cell_geometry_redo_kernel
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(64) void cell_moments_kernel(
     const float *__restrict__ points, uint32_t num_points, const uint32_t *__restrict__ adj,
@@ -45,64 +31,37 @@ __global__ __launch_bounds__(64) void cell_moments_kernel(
     __shared__ double s_t[2 * kLaneCap][kWave];
     const uint32_t a = blockIdx.x, lane = threadIdx.x;
     const uint32_t begin = offsets[a], end = offsets[a + 1];
-    if (begin > end || end > num_edges || end - begin > kWave) {   // wave-uniform
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (begin > end || end > num_edges || end - begin > kWave) return hand_on(redo, a, lane);   // wave-uniform
     const uint32_t degree = end - begin;
-    const bool have = lane < degree;
-    uint32_t q = have ? adj[begin + lane] : 0u;
-    bool bad = have && (q >= num_points || q == a);
-    if (!have || bad) q = a;
-    double dx, dy, dz, h;
-    clip::neighbour(points, a, q, dx, dy, dz, h);
-    bad = bad || (have && !(h > 0.0));
-    s_plane[0][lane] = dx, s_plane[1][lane] = dy, s_plane[2][lane] = dz, s_plane[3][lane] = h;
-    __syncthreads();
-    if (__any(bad)) {   // a malformed row says so in its status, bounded or not
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    const CellLane f = stage_row(points, num_points, adj, a, begin, degree, lane, s_plane);
+    if (sync_any_bad(f.bad)) return hand_on(redo, a, lane);   // a malformed row says so in its status, bounded or not
     clip::MomentSums sums = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, degree == 0 || !bounded[a]};
     if (sums.unbounded) {   // wave-uniform: no moments, and nothing is clipped
         if (lane == 0) {
             clip::write_moments(points, a, sums, volume, centroid, site_moment, central_moment);
-            redo[a] = 0;
+            keep(redo, a);
         }
         return;
     }
     const double R = clip::half_side(bbox);
     bool overflow = false;
-    if (have) {
-        const clip::Frame frame = clip::make_frame(dx, dy, dz);
+    if (f.have) {
+        const clip::Frame frame = clip::make_frame(f.dx, f.dy, f.dz);
         double *s = &s_s[0][lane], *t = &s_t[0][lane];
-        clip::init_square(s, t, kWave, R);
-        uint32_t m = 4, cur = 0;
-        for (uint32_t j = 0; j < degree && m != 0; ++j) {
-            if (j == lane) continue;
-            double A, B, C;
-            clip::plane_in_frame(frame, s_plane[0][j], s_plane[1][j], s_plane[2][j], s_plane[3][j], A, B, C);
-            const uint32_t in = cur * kLaneCap * kWave, out = (cur ^ 1u) * kLaneCap * kWave;
-            if (!clip::clip_step(s + in, t + in, s + out, t + out, kWave, kLaneCap, m, A, B, C)) {
-                overflow = true;
-                break;
-            }
-            cur ^= 1u;
+        const Clipped c = clip_by_row(frame, s_plane, degree, lane, R, s, t);
+        overflow = c.overflow;
+        if (!overflow) {
+            const uint32_t at = c.cur * kLaneCap * kWave;
+            clip::add_face_moment(sums, frame, clip::moments(s + at, t + at, kWave, c.m, R));
         }
-        if (!overflow)
-            clip::add_face_moment(sums, frame,
-                                  clip::moments(s + cur * kLaneCap * kWave, t + cur * kLaneCap * kWave, kWave, m, R));
     }
-    if (__any(overflow)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (__any(overflow)) return hand_on(redo, a, lane);
     sums.unbounded = __any(sums.unbounded);   // a face of a cell called bounded came out open: the geometry is not this row's
     sums.xx = wave_sum(sums.xx), sums.yy = wave_sum(sums.yy), sums.zz = wave_sum(sums.zz);
     sums.xy = wave_sum(sums.xy), sums.xz = wave_sum(sums.xz), sums.yz = wave_sum(sums.yz);
     if (lane == 0) {
         clip::write_moments(points, a, sums, volume, centroid, site_moment, central_moment);
-        redo[a] = 0;
+        keep(redo, a);
     }
 }
 
@@ -113,15 +72,11 @@ __global__ __launch_bounds__(64) void cell_moments_redo_kernel(
     double *__restrict__ site_moment, double *__restrict__ central_moment, const uint8_t *__restrict__ redo,
     uint8_t *__restrict__ cell_status) {
     __shared__ double s_s[2 * kWaveCap], s_t[2 * kWaveCap];
-    const uint32_t cell = blockIdx.x * kWave + threadIdx.x;
-    const bool mine = cell < num_points && redo[cell] != 0;
-    if (cell < num_points && !mine) cell_status[cell] = (uint8_t)clip::kCellOk;
-    unsigned long long todo = __ballot(mine);
+    unsigned long long todo = redo_todo(num_points, redo, cell_status);
     if (threadIdx.x != 0) return;
     const double R = clip::half_side(bbox);
     while (todo) {
-        const uint32_t a = blockIdx.x * kWave + (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1ull;
+        const uint32_t a = redo_next(todo);
         cell_status[a] = (uint8_t)clip::cell_moments_serial(points, num_points, adj, offsets, num_edges, a, R, s_s, s_t,
                                                             kWaveCap, volume, centroid, bounded, site_moment,
                                                             central_moment);
@@ -135,7 +90,7 @@ using namespace rf;
 
 extern "C" {
 
-size_t rf_cell_moments_workspace_bytes(uint32_t num_points) { return ((size_t)num_points + 255u) & ~(size_t)255u; }
+size_t rf_cell_moments_workspace_bytes(uint32_t num_points) { return redo_bytes(num_points); }
 
 int rf_cell_moments(const float *points, uint32_t num_points, const uint32_t *point_adjacency,
                     const uint32_t *point_adjacency_offsets, uint32_t num_edges, const float *bbox,
@@ -149,15 +104,10 @@ int rf_cell_moments(const float *points, uint32_t num_points, const uint32_t *po
         return fail(RF_ERR_INVALID_ARGUMENT, "rf_cell_moments: null pointer");
     if (!workspace || workspace_bytes < rf_cell_moments_workspace_bytes(num_points))
         return fail(RF_ERR_WORKSPACE, "rf_cell_moments: workspace missing or too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *redo = static_cast<uint8_t *>(workspace);
-    hipLaunchKernelGGL(cell_moments::cell_moments_kernel, dim3(num_points), dim3(cell_moments::kWave), 0, s, points, num_points,
-                       point_adjacency, point_adjacency_offsets, num_edges, bbox, volume, centroid, bounded,
-                       site_moment, central_moment, redo);
-    hipLaunchKernelGGL(cell_moments::cell_moments_redo_kernel, dim3((num_points + cell_moments::kWave - 1u) / cell_moments::kWave),
-                       dim3(cell_moments::kWave), 0, s, points, num_points, point_adjacency, point_adjacency_offsets,
-                       num_edges, bbox, volume, centroid, bounded, site_moment, central_moment, redo, cell_status);
-    return check_launch("rf_cell_moments");
+    return launch_cell_waves("rf_cell_moments", stream, num_points, workspace, cell_status,
+                             cell_moments::cell_moments_kernel, cell_moments::cell_moments_redo_kernel, points,
+                             num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, volume, centroid,
+                             bounded, site_moment, central_moment);
 }
 
 }  // extern "C"

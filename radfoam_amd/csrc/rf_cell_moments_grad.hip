@@ -1,16 +1,12 @@
 // rf_cell_moments_grad.hip -- point gradients of the cells' second moments ("Point gradients of the second
-// moments").  The mathematics and the per-face arithmetic: rf_clip_moments_grad.hpp, all in double.
+// moments").  The mathematics and the per-face arithmetic: rf_clip_moments_grad.hpp, all in double.  The wave scheme, its
+// LDS layout and the hand-off through redo[cell]: rf_cell_wave.hpp.
 //
-//   cell_moments_grad_kernel       one wave per cell, one lane per face, the layout of cell_geometry_grad_kernel: the
-//                                  row's planes staged in LDS, each lane's polygon in its vertex-major LDS slot (no
-//                                  per-lane arrays).  The lane clips its face again, takes the polygon's moments up to
-//                                  third order, reads its neighbour's twelve upstream numbers, centroid and bounded flag
-//                                  and forms its 3-vector; three __shfl_xor reductions, and lane 0 adds the direct term
-//                                  -2 V G m and writes the row.  Rows of more than 64 faces and polygons of more than
-//                                  kLaneCap vertices are handed on, unwritten, through redo[cell].
-//   cell_moments_grad_redo_kernel  one wave per 64 cells: the cells handed on are walked by lane 0, face after face
-//                                  (rf::clip::cell_moments_grad_serial, what the host harness runs), with kWaveCap
-//                                  vertices.
+//   cell_moments_grad_kernel       the lane clips its face again, takes the polygon's moments up to third order, reads
+//                                  its neighbour's twelve upstream numbers, centroid and bounded flag and forms its
+//                                  3-vector; three wave sums, and lane 0 adds the direct term -2 V G m and writes the
+//                                  row.  Rows of up to 64 faces.
+//   cell_moments_grad_redo_kernel  the cells handed on, by rf::clip::cell_moments_grad_serial.
 //
 // Row a is a gather over a's own adjacency row: every output element is written exactly once by a plain store, there are
 // no atomics, and the result is bit-reproducible.
@@ -19,21 +15,11 @@
 #include <stdint.h>
 
 #include "../../include/radfoam_hip_moments_grad.h"
+#include "rf_cell_wave.hpp"
 #include "rf_clip_moments_grad.hpp"
-#include "rf_host.hpp"
 
 namespace rf {
 namespace moments_grad {
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kLaneCap = 16;    // as cell_geometry_kernel: 32 KiB of polygons per wave
-constexpr uint32_t kWaveCap = 256;   // as cell_geometry_redo_kernel
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(64) void cell_moments_grad_kernel(
     const float *__restrict__ points, uint32_t num_points, const uint32_t *__restrict__ adj,
@@ -46,70 +32,43 @@ __global__ __launch_bounds__(64) void cell_moments_grad_kernel(
     __shared__ double s_t[2 * kLaneCap][kWave];
     const uint32_t a = blockIdx.x, lane = threadIdx.x;
     const uint32_t begin = offsets[a], end = offsets[a + 1];
-    if (begin > end || end > num_edges || end - begin > kWave) {   // wave-uniform
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (begin > end || end > num_edges || end - begin > kWave) return hand_on(redo, a, lane);   // wave-uniform
     const uint32_t degree = end - begin;
     if (degree == 0) {   // no neighbours: nothing depends on this site through its own row
         if (lane == 0) {
             grad_points[3 * (size_t)a] = grad_points[3 * (size_t)a + 1] = grad_points[3 * (size_t)a + 2] = 0.0;
-            redo[a] = 0;
+            keep(redo, a);
         }
         return;
     }
-    const bool have = lane < degree;
-    uint32_t q = have ? adj[begin + lane] : 0u;
-    bool bad = have && (q >= num_points || q == a);
-    if (!have || bad) q = a;
-    double dx, dy, dz, h;
-    clip::neighbour(points, a, q, dx, dy, dz, h);
-    bad = bad || (have && !(h > 0.0));
-    s_plane[0][lane] = dx, s_plane[1][lane] = dy, s_plane[2][lane] = dz, s_plane[3][lane] = h;
-    __syncthreads();
-    if (__any(bad)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    const CellLane f = stage_row(points, num_points, adj, a, begin, degree, lane, s_plane);
+    if (sync_any_bad(f.bad)) return hand_on(redo, a, lane);
     const double R = clip::half_side(bbox);
     bool overflow = false;
     double gx = 0.0, gy = 0.0, gz = 0.0;
-    if (have) {
-        const clip::Frame frame = clip::make_frame(dx, dy, dz);
+    if (f.have) {
+        const clip::Frame frame = clip::make_frame(f.dx, f.dy, f.dz);
         double *s = &s_s[0][lane], *t = &s_t[0][lane];
-        clip::init_square(s, t, kWave, R);
-        uint32_t m = 4, cur = 0;
-        for (uint32_t j = 0; j < degree && m != 0; ++j) {
-            if (j == lane) continue;
-            double A, B, C;
-            clip::plane_in_frame(frame, s_plane[0][j], s_plane[1][j], s_plane[2][j], s_plane[3][j], A, B, C);
-            const uint32_t in = cur * kLaneCap * kWave, out = (cur ^ 1u) * kLaneCap * kWave;
-            if (!clip::clip_step(s + in, t + in, s + out, t + out, kWave, kLaneCap, m, A, B, C)) {
-                overflow = true;
-                break;
-            }
-            cur ^= 1u;
-        }
+        const Clipped c = clip_by_row(frame, s_plane, degree, lane, R, s, t);
+        overflow = c.overflow;
         if (!overflow) {
-            const clip::Moments3 m3 = clip::moments3(s + cur * kLaneCap * kWave, t + cur * kLaneCap * kWave, kWave, m, R);
+            const uint32_t at = c.cur * kLaneCap * kWave;
+            const clip::Moments3 m3 = clip::moments3(s + at, t + at, kWave, c.m, R);
             if (!m3.m.unbounded) {   // q < num_points: no lane of this wave is bad
                 const clip::MomentTerm ca = clip::moment_term(points, a, a, centroid, bounded, grad_site_moment,
                                                               grad_central_moment);
-                const clip::MomentTerm cb = clip::moment_term(points, a, q, centroid, bounded, grad_site_moment,
+                const clip::MomentTerm cb = clip::moment_term(points, a, f.q, centroid, bounded, grad_site_moment,
                                                               grad_central_moment);
                 clip::add_face_moment_grad(frame, m3, ca, cb, gx, gy, gz);
             }
         }
     }
-    if (__any(overflow)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (__any(overflow)) return hand_on(redo, a, lane);
     gx = wave_sum(gx), gy = wave_sum(gy), gz = wave_sum(gz);
     if (lane == 0) {
         clip::add_direct_moment_grad(points, a, volume, centroid, bounded, grad_site_moment, gx, gy, gz);
         grad_points[3 * (size_t)a] = gx, grad_points[3 * (size_t)a + 1] = gy, grad_points[3 * (size_t)a + 2] = gz;
-        redo[a] = 0;
+        keep(redo, a);
     }
 }
 
@@ -120,15 +79,11 @@ __global__ __launch_bounds__(64) void cell_moments_grad_redo_kernel(
     const double *__restrict__ grad_site_moment, const double *__restrict__ grad_central_moment,
     double *__restrict__ grad_points, const uint8_t *__restrict__ redo, uint8_t *__restrict__ cell_status) {
     __shared__ double s_s[2 * kWaveCap], s_t[2 * kWaveCap];
-    const uint32_t cell = blockIdx.x * kWave + threadIdx.x;
-    const bool mine = cell < num_points && redo[cell] != 0;
-    if (cell < num_points && !mine) cell_status[cell] = (uint8_t)clip::kCellOk;
-    unsigned long long todo = __ballot(mine);
+    unsigned long long todo = redo_todo(num_points, redo, cell_status);
     if (threadIdx.x != 0) return;
     const double R = clip::half_side(bbox);
     while (todo) {
-        const uint32_t a = blockIdx.x * kWave + (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1ull;
+        const uint32_t a = redo_next(todo);
         cell_status[a] = (uint8_t)clip::cell_moments_grad_serial(points, num_points, adj, offsets, num_edges, a, R, s_s,
                                                                  s_t, kWaveCap, volume, centroid, bounded,
                                                                  grad_site_moment, grad_central_moment, grad_points);
@@ -142,9 +97,7 @@ using namespace rf;
 
 extern "C" {
 
-size_t rf_cell_moments_grad_workspace_bytes(uint32_t num_points) {
-    return ((size_t)num_points + 255u) & ~(size_t)255u;
-}
+size_t rf_cell_moments_grad_workspace_bytes(uint32_t num_points) { return redo_bytes(num_points); }
 
 int rf_cell_moments_grad(const float *points, uint32_t num_points, const uint32_t *point_adjacency,
                          const uint32_t *point_adjacency_offsets, uint32_t num_edges, const float *bbox,
@@ -158,16 +111,10 @@ int rf_cell_moments_grad(const float *points, uint32_t num_points, const uint32_
         return fail(RF_ERR_INVALID_ARGUMENT, "rf_cell_moments_grad: null pointer");
     if (!workspace || workspace_bytes < rf_cell_moments_grad_workspace_bytes(num_points))
         return fail(RF_ERR_WORKSPACE, "rf_cell_moments_grad: workspace missing or too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *redo = static_cast<uint8_t *>(workspace);
-    hipLaunchKernelGGL(moments_grad::cell_moments_grad_kernel, dim3(num_points), dim3(moments_grad::kWave), 0, s, points,
-                       num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, volume, centroid, bounded,
-                       grad_site_moment, grad_central_moment, grad_points, redo);
-    hipLaunchKernelGGL(moments_grad::cell_moments_grad_redo_kernel,
-                       dim3((num_points + moments_grad::kWave - 1u) / moments_grad::kWave), dim3(moments_grad::kWave), 0,
-                       s, points, num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, volume, centroid,
-                       bounded, grad_site_moment, grad_central_moment, grad_points, redo, cell_status);
-    return check_launch("rf_cell_moments_grad");
+    return launch_cell_waves("rf_cell_moments_grad", stream, num_points, workspace, cell_status,
+                             moments_grad::cell_moments_grad_kernel, moments_grad::cell_moments_grad_redo_kernel, points,
+                             num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, volume, centroid,
+                             bounded, grad_site_moment, grad_central_moment, grad_points);
 }
 
 }  // extern "C"

@@ -1,21 +1,18 @@
 // rf_face_area_grad.hip -- point gradients of the Voronoi face areas ("Point gradients of the face areas").
-// The mathematics, the labelled clipping and the per-edge arithmetic: rf_clip_area_grad.hpp, all in double.
+// The mathematics, the labelled clipping and the per-edge arithmetic: rf_clip_area_grad.hpp, all in double.  The wave
+// scheme, its LDS layout and the hand-off through redo[cell]: rf_cell_wave.hpp.
 //
 //   face_weight_kernel          the pre-pass, one wave per cell and one lane per slot: the effective weight G of every
 //                               slot (its own upstream plus its mate's, found by a search of the neighbour's row, each
 //                               masked by its own face_area) into an f64[E] workspace array, by plain stores.
-//   face_area_grad_kernel       one wave per cell, one lane per face, the layout of cell_geometry_grad_kernel: the row's
-//                               planes, neighbour indices and weights staged in LDS, each lane's polygon in its
-//                               vertex-major LDS slot with the labels beside it in the same layout (no per-lane arrays).
-//                               The lane clips its face again with labels and sums its edges' terms: per edge a search
-//                               of the row of b for G_bc of its label, then one pass over the staged planes for further
-//                               sites cocircular around an edge (none, off degenerate clouds), the sums per edge kept
-//                               in the polygon buffer the clipping left free; a triangle counts in the lane of its
-//                               larger face.  Three __shfl_xor reductions, and lane 0 writes the row.  Rows of more
-//                               than 64 faces and polygons of more than kLaneCap vertices are handed on, unwritten,
-//                               through redo[cell].
-//   face_area_grad_redo_kernel  one wave per 64 cells: the cells handed on are walked by lane 0, face after face
-//                               (rf::clip::face_area_grad_serial, what the host harness runs), with kWaveCap vertices.
+//   face_area_grad_kernel       beside the planes, the row's neighbour indices and weights are staged in LDS, and each
+//                               lane's polygon has its labels beside it in the same layout.  The lane clips its face
+//                               again with labels (its own loop: the labelled step) and sums its edges' terms: per edge
+//                               a search of the row of b for G_bc of its label, then one pass over the staged planes for
+//                               further sites cocircular around an edge (none, off degenerate clouds), the sums per edge
+//                               kept in the polygon buffer the clipping left free; a triangle counts in the lane of its
+//                               larger face.  Three wave sums, and lane 0 writes the row.  Rows of up to 64 faces.
+//   face_area_grad_redo_kernel  the cells handed on, by rf::clip::face_area_grad_serial.
 //
 // Row a is a gather over a's own adjacency row and one look-up per edge in a neighbour's: every output element is
 // written exactly once by a plain store, there are no atomics, and the result is bit-reproducible.
@@ -24,32 +21,13 @@
 #include <stdint.h>
 
 #include "../../include/radfoam_hip_face_area_grad.h"
+#include "rf_cell_wave.hpp"
 #include "rf_clip_area_grad.hpp"
-#include "rf_host.hpp"
 
 namespace rf {
 namespace face_area_grad {
 
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kLaneCap = 16;    // as cell_geometry_kernel: 32 KiB of polygons per wave
-constexpr uint32_t kWaveCap = 256;   // as cell_geometry_redo_kernel
 constexpr uint32_t kWeightWaves = 4;
-
-// the row of a as the wave staged it in LDS: planes[4][kWave] and the sites
-struct RowFromLds {
-    const double *planes;
-    const uint32_t *sites;
-    __device__ __forceinline__ uint32_t site(uint32_t j) const { return sites[j]; }
-    __device__ __forceinline__ void plane(uint32_t j, double &dx, double &dy, double &dz, double &h) const {
-        dx = planes[j], dy = planes[kWave + j], dz = planes[2 * kWave + j], h = planes[3 * kWave + j];
-    }
-};
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(kWave *kWeightWaves) void face_weight_kernel(
     uint32_t num_points, const uint32_t *__restrict__ adj, const uint32_t *__restrict__ offsets, uint32_t num_edges,
@@ -75,18 +53,17 @@ __global__ __launch_bounds__(64) void face_area_grad_kernel(
     __shared__ uint8_t s_l[2 * kLaneCap][kWave];     // labels, beside the vertices
     const uint32_t a = blockIdx.x, lane = threadIdx.x;
     const uint32_t begin = offsets[a], end = offsets[a + 1];
-    if (begin > end || end > num_edges || end - begin > kWave) {   // wave-uniform
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (begin > end || end > num_edges || end - begin > kWave) return hand_on(redo, a, lane);   // wave-uniform
     const uint32_t degree = end - begin;
     if (degree == 0) {   // no neighbours: no face of this site's own row
         if (lane == 0) {
             grad_points[3 * (size_t)a] = grad_points[3 * (size_t)a + 1] = grad_points[3 * (size_t)a + 2] = 0.0;
-            redo[a] = 0;
+            keep(redo, a);
         }
         return;
     }
+    // the staging of stage_row, spelled out: through the helper this kernel's code comes out in another order.  The load
+    // and the bad test are load_neighbour's of rf_cell_wave.hpp, line for line: keep the two in step.
     const bool have = lane < degree;
     uint32_t q = have ? adj[begin + lane] : 0u;
     bool bad = have && (q >= num_points || q == a);
@@ -97,11 +74,7 @@ __global__ __launch_bounds__(64) void face_area_grad_kernel(
     s_plane[0][lane] = dx, s_plane[1][lane] = dy, s_plane[2][lane] = dz, s_plane[3][lane] = h;
     s_q[lane] = q;
     s_g[lane] = have ? weight[begin + lane] : 0.0;
-    __syncthreads();
-    if (__any(bad)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (sync_any_bad(bad)) return hand_on(redo, a, lane);
     const double R = clip::area_grad_half_side(bbox);
     bool overflow = false;
     double gx = 0.0, gy = 0.0, gz = 0.0;
@@ -126,20 +99,17 @@ __global__ __launch_bounds__(64) void face_area_grad_kernel(
         }
         if (!overflow && m != 0) {   // q < num_points: no lane of this wave is bad
             const uint32_t at = cur * kLaneCap * kWave, free_at = (cur ^ 1u) * kLaneCap * kWave;
-            const RowFromLds row = {&s_plane[0][0], s_q};
+            const RowFromLds<kWave> row = {&s_plane[0][0], s_q};
             clip::add_polygon_terms(row, degree, lane, frame, dx, dy, dz, R, s + at, t + at, l + at, s + free_at,
                                     t + free_at, kWave, m, adj, offsets, num_edges, weight, q, s_g, face_area + begin, gx,
                                     gy, gz);
         }
     }
-    if (__any(overflow)) {
-        if (lane == 0) redo[a] = 1;
-        return;
-    }
+    if (__any(overflow)) return hand_on(redo, a, lane);
     gx = wave_sum(gx), gy = wave_sum(gy), gz = wave_sum(gz);
     if (lane == 0) {
         grad_points[3 * (size_t)a] = gx, grad_points[3 * (size_t)a + 1] = gy, grad_points[3 * (size_t)a + 2] = gz;
-        redo[a] = 0;
+        keep(redo, a);
     }
 }
 
@@ -150,15 +120,11 @@ __global__ __launch_bounds__(64) void face_area_grad_redo_kernel(
     const uint8_t *__restrict__ redo, uint8_t *__restrict__ cell_status) {
     __shared__ double s_s[2 * kWaveCap], s_t[2 * kWaveCap];
     __shared__ uint32_t s_l[2 * kWaveCap];
-    const uint32_t cell = blockIdx.x * kWave + threadIdx.x;
-    const bool mine = cell < num_points && redo[cell] != 0;
-    if (cell < num_points && !mine) cell_status[cell] = (uint8_t)clip::kCellOk;
-    unsigned long long todo = __ballot(mine);
+    unsigned long long todo = redo_todo(num_points, redo, cell_status);
     if (threadIdx.x != 0) return;
     const double R = clip::area_grad_half_side(bbox);
     while (todo) {
-        const uint32_t a = blockIdx.x * kWave + (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1ull;
+        const uint32_t a = redo_next(todo);
         cell_status[a] = (uint8_t)clip::face_area_grad_serial(points, num_points, adj, offsets, num_edges, a, R, s_s, s_t,
                                                               s_l, kWaveCap, face_area, weight, grad_points);
     }
@@ -168,10 +134,6 @@ __global__ __launch_bounds__(64) void face_area_grad_redo_kernel(
 }  // namespace rf
 
 using namespace rf;
-
-static size_t redo_bytes(uint32_t num_points) {
-    return ((size_t)num_points + 255u) & ~(size_t)255u;
-}
 
 extern "C" {
 
@@ -190,22 +152,16 @@ int rf_face_area_grad(const float *points, uint32_t num_points, const uint32_t *
         return fail(RF_ERR_INVALID_ARGUMENT, "rf_face_area_grad: null pointer");
     if (!workspace || workspace_bytes < rf_face_area_grad_workspace_bytes(num_points, num_edges))
         return fail(RF_ERR_WORKSPACE, "rf_face_area_grad: workspace missing or too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *redo = static_cast<uint8_t *>(workspace);
-    double *weight = reinterpret_cast<double *>(redo + redo_bytes(num_points));
+    double *weight = reinterpret_cast<double *>(static_cast<uint8_t *>(workspace) + redo_bytes(num_points));
     if (num_edges)
         hipLaunchKernelGGL(face_area_grad::face_weight_kernel,
                            dim3((num_points + face_area_grad::kWeightWaves - 1u) / face_area_grad::kWeightWaves),
-                           dim3(face_area_grad::kWave * face_area_grad::kWeightWaves), 0, s, num_points, point_adjacency,
-                           point_adjacency_offsets, num_edges, face_area, grad_face_area, weight);
-    hipLaunchKernelGGL(face_area_grad::face_area_grad_kernel, dim3(num_points), dim3(face_area_grad::kWave), 0, s, points,
-                       num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, face_area, weight, grad_points,
-                       redo);
-    hipLaunchKernelGGL(face_area_grad::face_area_grad_redo_kernel,
-                       dim3((num_points + face_area_grad::kWave - 1u) / face_area_grad::kWave),
-                       dim3(face_area_grad::kWave), 0, s, points, num_points, point_adjacency, point_adjacency_offsets,
-                       num_edges, bbox, face_area, weight, grad_points, redo, cell_status);
-    return check_launch("rf_face_area_grad");
+                           dim3(kWave * face_area_grad::kWeightWaves), 0, static_cast<hipStream_t>(stream), num_points,
+                           point_adjacency, point_adjacency_offsets, num_edges, face_area, grad_face_area, weight);
+    return launch_cell_waves("rf_face_area_grad", stream, num_points, workspace, cell_status,
+                             face_area_grad::face_area_grad_kernel, face_area_grad::face_area_grad_redo_kernel, points,
+                             num_points, point_adjacency, point_adjacency_offsets, num_edges, bbox, face_area,
+                             weight, grad_points);
 }
 
 }  // extern "C"

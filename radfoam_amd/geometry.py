@@ -104,27 +104,39 @@ def _prepare(points, point_adjacency, point_adjacency_offsets):
     return p, adj, off, bbox
 
 
-def _run_geometry(p, adj, off, bbox):
-    """(CellGeometry, face_vertices int32[E]); one synchronisation, to read whether a cell was refused."""
+def _opt(t):
+    return None if t is None else _ptr(t)
+
+
+def _run_cells(name, entry, p, adj, off, bbox, *tensors, six=(), edge_workspace=False):
+    """Calls ``rf_<entry>`` of the library: (points, N, adjacency, offsets, E, bbox, *six, *tensors, status, workspace,
+    bytes, stream), a tensor that is None going as a null pointer.  One synchronisation, to read whether a cell was
+    refused; then RuntimeError "<name>: cell <i> is not supported: ..."."""
     n, e, dev = p.size(0), adj.numel(), p.device
     lib = _lib.load()
-    volume = torch.empty(n, dtype=torch.float64, device=dev)
-    centroid = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    bounded = torch.empty(n, dtype=torch.uint8, device=dev)
-    face_area = torch.empty(e, dtype=torch.float64, device=dev)
-    face_vertices = torch.empty(e, dtype=torch.int32, device=dev)
     status = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(int(lib.rf_cell_geometry_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
+    size = getattr(lib, f"rf_{entry}_workspace_bytes")
+    ws = torch.empty(max(int(size(n, e) if edge_workspace else size(n)), 256), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.rf_cell_geometry(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(volume), _ptr(centroid),
-                                  _ptr(bounded), _ptr(face_area), _ptr(face_vertices), _ptr(status), _ptr(ws),
-                                  ws.numel(), _stream(dev))
+        rc = getattr(lib, f"rf_{entry}")(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), *six, *map(_opt, tensors),
+                                         _ptr(status), _ptr(ws), ws.numel(), _stream(dev))
     _lib.check(rc)
     if n:
         worst, cell = status.max(0)
         worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
         if worst:
-            raise RuntimeError(f"cell_geometry: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+            raise RuntimeError(f"{name}: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+
+
+def _run_geometry(p, adj, off, bbox):
+    """(CellGeometry, face_vertices int32[E]); one synchronisation, to read whether a cell was refused."""
+    n, e, dev = p.size(0), adj.numel(), p.device
+    volume = torch.empty(n, dtype=torch.float64, device=dev)
+    centroid = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    bounded = torch.empty(n, dtype=torch.uint8, device=dev)
+    face_area = torch.empty(e, dtype=torch.float64, device=dev)
+    face_vertices = torch.empty(e, dtype=torch.int32, device=dev)
+    _run_cells("cell_geometry", "cell_geometry", p, adj, off, bbox, volume, centroid, bounded, face_area, face_vertices)
     return CellGeometry(volume, centroid, bounded.bool(), face_area), face_vertices
 
 
@@ -164,7 +176,6 @@ def _run_geometry_in_box(p, adj, off, bbox, six):
     """(BoxedCellGeometry, face_vertices int32[E], wall_vertices int32[N,6]); one synchronisation, to read whether a cell
     was refused."""
     n, e, dev = p.size(0), adj.numel(), p.device
-    lib = _lib.load()
     volume = torch.empty(n, dtype=torch.float64, device=dev)
     centroid = torch.empty((n, 3), dtype=torch.float64, device=dev)
     nonempty = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -172,18 +183,8 @@ def _run_geometry_in_box(p, adj, off, bbox, six):
     face_vertices = torch.empty(e, dtype=torch.int32, device=dev)
     wall_area = torch.empty((n, 6), dtype=torch.float64, device=dev)
     wall_vertices = torch.empty((n, 6), dtype=torch.int32, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(int(lib.rf_cell_box_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.rf_cell_box(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), *six, _ptr(volume), _ptr(centroid),
-                             _ptr(nonempty), _ptr(face_area), _ptr(face_vertices), _ptr(wall_area), _ptr(wall_vertices),
-                             _ptr(status), _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(rc)
-    if n:
-        worst, cell = status.max(0)
-        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
-        if worst:
-            raise RuntimeError(f"cell_geometry_in_box: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    _run_cells("cell_geometry_in_box", "cell_box", p, adj, off, bbox, volume, centroid, nonempty, face_area,
+               face_vertices, wall_area, wall_vertices, six=six)
     return BoxedCellGeometry(volume, centroid, nonempty.bool(), face_area, wall_area), face_vertices, wall_vertices
 
 
@@ -208,23 +209,9 @@ def cell_geometry_in_box(points: torch.Tensor, point_adjacency: torch.Tensor, po
 
 def _run_geometry_in_box_grad(p, adj, off, bbox, six, volume, centroid, nonempty, grad_volume, grad_centroid):
     """grad_points f64[N,3]; one synchronisation, to read whether a row was refused."""
-    n, e, dev = p.size(0), adj.numel(), p.device
-    lib = _lib.load()
-    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(int(lib.rf_cell_box_grad_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
-    opt = lambda t: None if t is None else _ptr(t)
-    with torch.cuda.device(dev):
-        rc = lib.rf_cell_box_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), *six, _ptr(volume), _ptr(centroid),
-                                  _ptr(nonempty), opt(grad_volume), opt(grad_centroid), _ptr(grad), _ptr(status),
-                                  _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(rc)
-    if n:
-        worst, cell = status.max(0)
-        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
-        if worst:
-            raise RuntimeError(f"cell_geometry_in_box_grad: cell {cell} is not supported: "
-                               f"{_STATUS_TEXT.get(worst, worst)}")
+    grad = torch.empty((p.size(0), 3), dtype=torch.float64, device=p.device)
+    _run_cells("cell_geometry_in_box_grad", "cell_box_grad", p, adj, off, bbox, volume, centroid, nonempty, grad_volume,
+               grad_centroid, grad, six=six)
     return grad
 
 
@@ -266,23 +253,9 @@ def cell_geometry_in_box_grad(points: torch.Tensor, point_adjacency: torch.Tenso
 def _run_face_area_in_box_grad(p, adj, off, bbox, six, volume, centroid, nonempty, face_area, wall_area, grad_face_area,
                                 grad_wall_area):
     """grad_points f64[N,3]; one synchronisation, to read whether a row was refused."""
-    n, e, dev = p.size(0), adj.numel(), p.device
-    lib = _lib.load()
-    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(int(lib.rf_cell_box_area_grad_workspace_bytes(n, e)), 256), dtype=torch.uint8, device=dev)
-    opt = lambda t: None if t is None else _ptr(t)
-    with torch.cuda.device(dev):
-        rc = lib.rf_cell_box_area_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), *six, _ptr(volume),
-                                       _ptr(centroid), _ptr(nonempty), _ptr(face_area), _ptr(wall_area),
-                                       opt(grad_face_area), opt(grad_wall_area), _ptr(grad), _ptr(status), _ptr(ws),
-                                       ws.numel(), _stream(dev))
-    _lib.check(rc)
-    if n:
-        worst, cell = status.max(0)
-        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
-        if worst:
-            raise RuntimeError(f"face_area_in_box_grad: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    grad = torch.empty((p.size(0), 3), dtype=torch.float64, device=p.device)
+    _run_cells("face_area_in_box_grad", "cell_box_area_grad", p, adj, off, bbox, volume, centroid, nonempty, face_area,
+               wall_area, grad_face_area, grad_wall_area, grad, six=six, edge_workspace=True)
     return grad
 
 
@@ -407,22 +380,10 @@ def cell_moments(points: torch.Tensor, point_adjacency: torch.Tensor, point_adja
 
 def _run_moments_in_box(p, adj, off, bbox, six, volume, centroid, nonempty):
     """(site f64[N,6], central f64[N,6]); one synchronisation, to read whether a cell was refused."""
-    n, e, dev = p.size(0), adj.numel(), p.device
-    lib = _lib.load()
-    site = torch.empty((n, 6), dtype=torch.float64, device=dev)
-    central = torch.empty((n, 6), dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(int(lib.rf_cell_box_moments_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.rf_cell_box_moments(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), *six, _ptr(volume),
-                                     _ptr(centroid), _ptr(nonempty), _ptr(site), _ptr(central), _ptr(status), _ptr(ws),
-                                     ws.numel(), _stream(dev))
-    _lib.check(rc)
-    if n:
-        worst, cell = status.max(0)
-        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
-        if worst:
-            raise RuntimeError(f"cell_moments_in_box: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    site = torch.empty((p.size(0), 6), dtype=torch.float64, device=p.device)
+    central = torch.empty((p.size(0), 6), dtype=torch.float64, device=p.device)
+    _run_cells("cell_moments_in_box", "cell_box_moments", p, adj, off, bbox, volume, centroid, nonempty, site, central,
+               six=six)
     return site, central
 
 
@@ -504,22 +465,9 @@ def _upstream(name, t, shape, device):
 
 def _run_geometry_grad(p, adj, off, bbox, volume, centroid, bounded, grad_volume, grad_centroid):
     """grad_points f64[N,3]; one synchronisation, to read whether a row was refused."""
-    n, e, dev = p.size(0), adj.numel(), p.device
-    lib = _lib.load()
-    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(int(lib.rf_cell_geometry_grad_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
-    opt = lambda t: None if t is None else _ptr(t)
-    with torch.cuda.device(dev):
-        rc = lib.rf_cell_geometry_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(volume), _ptr(centroid),
-                                       _ptr(bounded), opt(grad_volume), opt(grad_centroid), _ptr(grad), _ptr(status),
-                                       _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(rc)
-    if n:
-        worst, cell = status.max(0)
-        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
-        if worst:
-            raise RuntimeError(f"cell_geometry_grad: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    grad = torch.empty((p.size(0), 3), dtype=torch.float64, device=p.device)
+    _run_cells("cell_geometry_grad", "cell_geometry_grad", p, adj, off, bbox, volume, centroid, bounded, grad_volume,
+               grad_centroid, grad)
     return grad
 
 
@@ -548,20 +496,9 @@ def cell_geometry_grad(points: torch.Tensor, point_adjacency: torch.Tensor, poin
 
 def _run_face_area_grad(p, adj, off, bbox, face_area, grad_face_area):
     """grad_points f64[N,3]; one synchronisation, to read whether a row was refused."""
-    n, e, dev = p.size(0), adj.numel(), p.device
-    lib = _lib.load()
-    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(int(lib.rf_face_area_grad_workspace_bytes(n, e)), 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.rf_face_area_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(face_area),
-                                   _ptr(grad_face_area), _ptr(grad), _ptr(status), _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(rc)
-    if n:
-        worst, cell = status.max(0)
-        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
-        if worst:
-            raise RuntimeError(f"face_area_grad: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    grad = torch.empty((p.size(0), 3), dtype=torch.float64, device=p.device)
+    _run_cells("face_area_grad", "face_area_grad", p, adj, off, bbox, face_area, grad_face_area, grad,
+               edge_workspace=True)
     return grad
 
 
@@ -623,43 +560,17 @@ class _DifferentiableCellGeometry(torch.autograd.Function):
 
 def _run_moments(p, adj, off, bbox, volume, centroid, flags):
     """(site f64[N,6], central f64[N,6]); one synchronisation, to read whether a cell was refused."""
-    n, e, dev = p.size(0), adj.numel(), p.device
-    lib = _lib.load()
-    site = torch.empty((n, 6), dtype=torch.float64, device=dev)
-    central = torch.empty((n, 6), dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(int(lib.rf_cell_moments_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.rf_cell_moments(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(volume), _ptr(centroid),
-                                 _ptr(flags), _ptr(site), _ptr(central), _ptr(status), _ptr(ws), ws.numel(),
-                                 _stream(dev))
-    _lib.check(rc)
-    if n:
-        worst, cell = status.max(0)
-        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
-        if worst:
-            raise RuntimeError(f"cell_moments: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    site = torch.empty((p.size(0), 6), dtype=torch.float64, device=p.device)
+    central = torch.empty((p.size(0), 6), dtype=torch.float64, device=p.device)
+    _run_cells("cell_moments", "cell_moments", p, adj, off, bbox, volume, centroid, flags, site, central)
     return site, central
 
 
 def _run_moments_grad(p, adj, off, bbox, volume, centroid, bounded, grad_site_moment, grad_central_moment):
     """grad_points f64[N,3]; one synchronisation, to read whether a row was refused."""
-    n, e, dev = p.size(0), adj.numel(), p.device
-    lib = _lib.load()
-    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(int(lib.rf_cell_moments_grad_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
-    opt = lambda t: None if t is None else _ptr(t)
-    with torch.cuda.device(dev):
-        rc = lib.rf_cell_moments_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), _ptr(volume), _ptr(centroid),
-                                      _ptr(bounded), opt(grad_site_moment), opt(grad_central_moment), _ptr(grad),
-                                      _ptr(status), _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(rc)
-    if n:
-        worst, cell = status.max(0)
-        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
-        if worst:
-            raise RuntimeError(f"cell_moments_grad: cell {cell} is not supported: {_STATUS_TEXT.get(worst, worst)}")
+    grad = torch.empty((p.size(0), 3), dtype=torch.float64, device=p.device)
+    _run_cells("cell_moments_grad", "cell_moments_grad", p, adj, off, bbox, volume, centroid, bounded,
+               grad_site_moment, grad_central_moment, grad)
     return grad
 
 
@@ -750,24 +661,9 @@ def _run_moments_in_box_grad(p, adj, off, bbox, six, volume, centroid, nonempty,
                              grad_volume, grad_centroid):
     """grad_points f64[N,3]; one launch of the fused operator and one synchronisation, to read whether a row was
     refused."""
-    n, e, dev = p.size(0), adj.numel(), p.device
-    lib = _lib.load()
-    grad = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(int(lib.rf_cell_box_moments_grad_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
-    opt = lambda t: None if t is None else _ptr(t)
-    with torch.cuda.device(dev):
-        rc = lib.rf_cell_box_moments_grad(_ptr(p), n, _ptr(adj), _ptr(off), e, _ptr(bbox), *six, _ptr(volume),
-                                          _ptr(centroid), _ptr(nonempty), opt(grad_site_moment),
-                                          opt(grad_central_moment), opt(grad_volume), opt(grad_centroid), _ptr(grad),
-                                          _ptr(status), _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(rc)
-    if n:
-        worst, cell = status.max(0)
-        worst, cell = torch.stack([worst.to(torch.int64), cell]).tolist()      # the one synchronisation
-        if worst:
-            raise RuntimeError(f"cell_moments_in_box_grad: cell {cell} is not supported: "
-                               f"{_STATUS_TEXT.get(worst, worst)}")
+    grad = torch.empty((p.size(0), 3), dtype=torch.float64, device=p.device)
+    _run_cells("cell_moments_in_box_grad", "cell_box_moments_grad", p, adj, off, bbox, volume, centroid, nonempty,
+               grad_site_moment, grad_central_moment, grad_volume, grad_centroid, grad, six=six)
     return grad
 
 

@@ -37,7 +37,7 @@ def test_sources_are_built_but_not_part_of_the_source_hash():
 
     names = lambda paths: {os.path.basename(p) for p in paths}
     assert "rf_cell_geometry_grad.hip" in names(build.EXTRA_SOURCES)
-    assert {"rf_clip_grad.hpp", "radfoam_hip_geometry_grad.h"} <= names(build.EXTRA_HEADERS)
+    assert {"rf_clip_grad.hpp", "rf_cell_wave.hpp", "radfoam_hip_geometry_grad.h"} <= names(build.EXTRA_HEADERS)
     assert not names(build.SOURCES + build.HEADERS) & names(build.EXTRA_SOURCES + build.EXTRA_HEADERS)
     lib = _lib.load()
     for name in ("rf_cell_geometry_grad", "rf_cell_geometry_grad_workspace_bytes"):
