@@ -13,6 +13,7 @@ from .geometry import (BoxedCellGeometry, BoxedCellMoments, CellGeometry, CellMo
                        cell_moments_grad, cell_moments_in_box, cell_moments_in_box_grad, cell_surface,
                        differentiable_cell_geometry, differentiable_cell_geometry_in_box, differentiable_cell_moments,
                        differentiable_cell_moments_in_box, face_area_grad, face_area_in_box_grad)
+from .isosurface import IsoMesh, isosurface, isosurface_vertices, isosurface_vertices_grad
 from .mesh import CellMesh, cell_mesh, mesh_vertices, mesh_vertices_grad
 from .pipeline import Pipeline, create_pipeline, invalidate_caches
 from .scene_ops import pack_attributes
@@ -32,5 +33,6 @@ __all__ = [
     "mesh_vertices", "mesh_vertices_grad", "CellMoments", "cell_moments", "cell_moments_grad",
     "differentiable_cell_moments", "BoxedCellGeometry", "cell_geometry_in_box",
     "cell_geometry_in_box_grad", "differentiable_cell_geometry_in_box", "BoxedCellMoments", "cell_moments_in_box",
-    "cell_moments_in_box_grad", "differentiable_cell_moments_in_box", "face_area_in_box_grad",
+    "cell_moments_in_box_grad", "differentiable_cell_moments_in_box", "face_area_in_box_grad", "IsoMesh", "isosurface",
+    "isosurface_vertices", "isosurface_vertices_grad",
 ]

@@ -67,7 +67,8 @@ class LaunchOpts(C.Structure):
 # every symbol include/radfoam_hip.h, radfoam_hip_geometry.h, radfoam_hip_geometry_grad.h, radfoam_hip_segments.h,
 # radfoam_hip_composite.h, radfoam_hip_distortion.h, radfoam_hip_quantiles.h, radfoam_hip_cell_reduce.h,
 # radfoam_hip_sh_entries.h, radfoam_hip_entry_weights.h, radfoam_hip_face_area_grad.h, radfoam_hip_mesh.h, radfoam_hip_moments.h,
-# radfoam_hip_moments_grad.h, radfoam_hip_box.h, radfoam_hip_box_grad.h, radfoam_hip_box_moments.h and radfoam_hip_box_area_grad.h declare:
+# radfoam_hip_moments_grad.h, radfoam_hip_box.h, radfoam_hip_box_grad.h, radfoam_hip_box_moments.h, radfoam_hip_box_area_grad.h
+# and radfoam_hip_isosurface.h declare:
 # name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -172,6 +173,10 @@ SYMBOLS = {
     "rf_cell_box_moments_grad": (_INT, [_P, _U32, _P, _P, _U32, _P] + [C.c_double] * 6 + [_P] * 10 + [C.c_size_t, _P]),
     "rf_cell_box_area_grad_workspace_bytes": (C.c_size_t, [_U32, _U32]),
     "rf_cell_box_area_grad": (_INT, [_P, _U32, _P, _P, _U32, _P] + [C.c_double] * 6 + [_P] * 10 + [C.c_size_t, _P]),
+    "rf_isosurface_count": (_INT, [_P, _U32, _U32, _P, _U32, C.c_double, _P, _P, _P]),
+    "rf_isosurface_emit": (_INT, [_P, _U32, _U32, _P, _P, _U32, C.c_double, _P, _P, C.c_int64, _P, _P, _P]),
+    "rf_isosurface_vertices": (_INT, [_P, _P, _U32, _P, _U32, C.c_double, _P, _P, _P]),
+    "rf_isosurface_vertices_grad": (_INT, [_P, _P, _U32, _P, _U32, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None
