@@ -41,6 +41,7 @@
 #include "../../include/radfoam_hip.h"
 #include "rf_foam.hpp"
 #include "rf_host.hpp"
+#include "rf_epoch.hpp"
 #include "rf_math.hpp"
 #include "rf_tiles.hpp"
 #include "rf_wave.hpp"
@@ -1758,7 +1759,7 @@ __global__ __launch_bounds__(kBlock) void backward_replay_kernel(BwdParams p) {
 //   * lanes of a wave in the same cell are first merged in registers (DPP xor stages), which cuts
 //     the lanes per address;
 //   * rows of doubles are large (248 B at SH degree 2: 160 rows in the 40 KB a block may use at 4
-//     blocks per CU; 424 B at degree 3: 124 rows at 3 blocks per CU), so the table is flushed often: every kEpoch steps the block synchronises and
+//     blocks per CU; 424 B at degree 3: 124 rows at 3 blocks per CU), so the table is flushed often: every kEpoch steps (kEpochLong while only density sums arrive) the block synchronises and
 //     evicts the rows that were not touched during the epoch (the walk has moved past those cells)
 //     with one coalesced row of global atomics each, skipping zeros; rows still in use stay.
 //     A lane whose key finds no free row adds straight to global memory instead (must stay rare:
@@ -1812,11 +1813,21 @@ __global__ __launch_bounds__(kBlock) void backward_replay_kernel(BwdParams p) {
 //     the wide rows go through the cooperative loop.
 // Measured on the benchmark frame (profiles/r07/b_image_backward_flush_ab.log): backward 3.75 -> 3.60 ms.  A block
 // evicts 17 rows per epoch, 13 of them narrow.
-// Measured out in the same log, each on top of the narrow pass:
-//   * the block's "is any lane alive" through a flag word in LDS between the epoch's own two barriers instead of
-//     __syncthreads_or (which brings two barriers of its own): 0.01-0.07 ms better in each of six alternating pairs of
-//     runs, but less than the runs of one build differ among themselves -- the waves wait at the epoch's first
-//     barrier for the slowest of them (12 % of the wave clocks), not for the barrier instructions;
+// The epoch's length follows the table (rf_epoch.hpp; profiles/r08/b_image_backward_epoch_ab.log): 78 % of the
+// benchmark frame's block-epochs add density sums only, so after a flush that leaves no wide row and at most
+// RF_CACHE_EPOCH_LONG_ROWS rows the next epoch runs RF_CACHE_EPOCH_LONG = 8 steps, and the flush that ends it evicts
+// every narrow row.  Backward 3.60-3.62 -> 3.51-3.55 ms, and with the alive vote on the epoch word
+// (RF_EPOCH_FLAG_VOTE) 3.42-3.43.  Measured out in the same log:
+//   * long epochs that keep the touched narrow rows ("untouched for a whole epoch" as in the short ones): 8 steps
+//     3.63 ms, 16 steps 3.78 -- rows stay twice as long, the table fills and lane adds bypass it;
+//   * long epochs of 12 and 16 steps: within 0.02 ms of 8; 32 steps: 4.11-4.13 ms;
+//   * no threshold on the resident rows (160): 0.02 ms slower than 48; 16 equals 48;
+//   * every narrow row evicted at every flush, short epochs included: 0.003-0.02 ms better than at long ones only,
+//     not told from noise in two rounds.  (With fixed epochs of 4 steps that rule alone gives 3.47 against 3.56 ms:
+//     most of what the long epochs win is the table relieved of narrow rows, not the barriers saved.)
+// The alive vote through the word was within noise in round 7 (same log as the narrow pass: 0.01-0.07 ms better in each
+// of six pairs); it also takes __syncthreads_or's 256 bytes of LDS and the instance's 12 bytes of scratch away.
+// Measured out in round 7, each on top of the narrow pass:
 //   * rows dealt to the waves (wave w, lane l owns row 4 l + w, so that the four waves evict equal shares instead of
 //     waves 0 and 1 owning most rows) and the evicted row's key by v_readlane instead of __shfl in the cooperative
 //     loop: nothing either way.  With 4 wide rows per block-epoch the loop is one or two trips and the closing barrier
@@ -1830,8 +1841,27 @@ __global__ __launch_bounds__(kBlock) void backward_replay_kernel(BwdParams p) {
 #else
 #define RF_WIDE_MARKS 0
 #endif
+// The epoch's length (rf_epoch.hpp): RF_CACHE_EPOCH steps while wide rows are resident, RF_CACHE_EPOCH_LONG while at
+// most RF_CACHE_EPOCH_LONG_ROWS rows, all of them narrow, are.
+// The flush that ends a long epoch evicts every narrow row, touched or not (one read and at most one atomic by the
+// owner; a later re-claim is one CAS): "untouched for a whole epoch" would double a row's stay with the epoch.
+//   RF_EPOCH_FLAG_VOTE: the block's "is any lane alive" rides on the epoch word instead of __syncthreads_or (which
+//     brings two barriers of its own and 256 bytes of LDS); a block that turns out dead flushes what is left after
+//     the loop.
+#ifndef RF_EPOCH_FLAG_VOTE
+#define RF_EPOCH_FLAG_VOTE 1
+#endif
 constexpr int kCacheProbes = RF_CACHE_PROBES;
 constexpr uint32_t kEpoch = RF_CACHE_EPOCH;
+constexpr uint32_t kEpochLong = RF_CACHE_EPOCH_LONG;
+static_assert(kEpoch >= 1u && kEpochLong >= kEpoch, "the long epoch is no shorter than the short one");
+static_assert(kBlock / 64 <= 15, "the epoch word counts waves in four bits");
+// the sections build reads the resident rows off the word whatever the epochs do
+#if RF_CACHE_EPOCH_LONG != RF_CACHE_EPOCH || RF_EPOCH_FLAG_VOTE || defined(RF_EXPERIMENT_SECTIONS)
+#define RF_EPOCH_WORD 1
+#else
+#define RF_EPOCH_WORD 0
+#endif
 
 // One stage of the in-register pre-reduction that precedes the LDS adds: lanes l and l^BIT that
 // both hold a contribution for the same key are merged into the lower lane; the upper lane drops
@@ -1880,6 +1910,13 @@ __device__ __forceinline__ int cache_find(uint32_t *keys, uint32_t key) {
 struct FlushRecord {
     unsigned long long arrive = 0, body = 0, close = 0;   // until the first barrier releases / the flush / the closing barrier
     unsigned long long epochs = 0, wide = 0, narrow = 0, bypass = 0;   // rows evicted by this wave; lane adds that found no row
+    // `arrive` and the wave-epochs split two ways: the wave still had a live lane in the epoch (live) or had finished
+    // (done); the block added colour or point gradients in the epoch (lit) or density sums only (dens)
+    unsigned long long arr_live_lit = 0, arr_live_dens = 0, arr_done_lit = 0, arr_done_dens = 0;
+    unsigned long long n_live_lit = 0, n_live_dens = 0, n_done_lit = 0, n_done_dens = 0;
+    // rows resident after the flush, per kind of block-epoch (the same in all four waves), and the long epochs begun
+    unsigned long long res_sum_lit = 0, res_sum_dens = 0, res_max_lit = 0, res_max_dens = 0, n_lit = 0, n_dens = 0, n_long = 0;
+    bool wave_live = false, wave_lit = false;   // of the running epoch
 };
 #endif
 
@@ -1888,6 +1925,7 @@ struct FlushRecord {
 // evicted by a wave are then written by the whole wave, two rows per trip, 32 lanes per row.
 template <int NB>
 __device__ __forceinline__ void cache_flush(double *rows, uint32_t *keys, uint8_t *touch, uint8_t *wide, bool all,
+                                              bool all_narrow, uint32_t *word, uint32_t word_extra,
                                               float *attr_grad, float *points_grad, uint32_t pitch
 #ifdef RF_EXPERIMENT_SECTIONS
                                               , FlushRecord &rec
@@ -1900,8 +1938,21 @@ __device__ __forceinline__ void cache_flush(double *rows, uint32_t *keys, uint8_
     const uint32_t my_row = threadIdx.x;   // thread t owns row t
     const uint32_t my_key = mine_exists ? keys[my_row] : kNone;
     const bool occupied = my_key != kNone;
-    const bool evict = occupied && (all || touch[my_row] == (uint8_t)0);
+#if RF_WIDE_MARKS
+    const bool marked = occupied && wide[my_row] != (uint8_t)0;
+#else
+    const bool marked = occupied;   // no marks: every row counts as wide
+#endif
+    const bool evict = occupied && (all || touch[my_row] == (uint8_t)0 || (all_narrow && !marked));
     if (occupied && !evict) touch[my_row] = (uint8_t)0;
+#if RF_EPOCH_WORD
+    // what this wave leaves in the table, for the length of the next epoch (one LDS atomic per wave)
+    if (word != nullptr) {
+        const unsigned long long stay = ballot(occupied && !evict);
+        const bool stay_wide = ballot(occupied && !evict && marked) != 0ull;
+        if (lane == 0u) atomicAdd(word, epoch_word((uint32_t)__builtin_popcountll(stay), stay_wide) + word_extra);
+    }
+#endif
 #if RF_WIDE_MARKS
     bool is_wide = false;
 #endif
@@ -1909,7 +1960,7 @@ __device__ __forceinline__ void cache_flush(double *rows, uint32_t *keys, uint8_
         keys[my_row] = kNone;
 #if RF_WIDE_MARKS
         // a row keeps its mark from the first colour or point-gradient add until it is evicted
-        is_wide = wide[my_row] != (uint8_t)0;
+        is_wide = marked;
         if (is_wide) wide[my_row] = (uint8_t)0;
 #endif
 #if RF_FLUSH_NARROW
@@ -2076,6 +2127,11 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
 #else
     uint8_t *const s_wide = nullptr;
 #endif
+    // the epoch words: flush n adds to word n & 1 and clears the other one for flush n + 1
+#if RF_EPOCH_WORD
+    __shared__ uint32_t s_epoch[2];
+    if (threadIdx.x < 2u) s_epoch[threadIdx.x] = 0u;
+#endif
     for (uint32_t i = threadIdx.x; i < (uint32_t)(ROWS * STRIDE); i += kBlock) s_rows[i] = 0.0;
     for (uint32_t i = threadIdx.x; i < (uint32_t)ROWS; i += kBlock) {
         s_keys[i] = kNone;
@@ -2092,8 +2148,22 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
 
     StepGrad G;
     clear_step(G);
-    uint32_t it = 0;
     bool block_alive = true;
+    // Why no wave can miss a barrier although the epochs differ in length: `left` goes down by one per trip in all
+    // four waves, whether a wave still steps or not, because the loop condition block_alive is block-uniform (a
+    // barrier's vote, or the epoch word read after the closing barrier).  Its next start value is a function of the
+    // epoch word alone (rf_epoch.hpp); the word of flush n is written only between the two barriers of flush n - 1
+    // (cleared) and of flush n (the waves' adds) and read only after the closing barrier of flush n; nothing on the
+    // step path writes it and nothing a wave sees on the step path enters the length.  So `left` is block-uniform
+    // too, and every wave reaches every barrier the same number of times.  A table that fills up during a long epoch
+    // is safe as it always was: cache_find returns -1 and the lane adds straight to memory.
+    // (`left` counts down instead of comparing a step counter with the step of the next flush: one value less to
+    // carry round the loop, which at 128 VGPRs is the difference between 12 and 20 bytes of scratch.)
+    uint32_t left = kEpoch;      // steps until the next flush
+#if RF_EPOCH_WORD
+    uint32_t parity = 0u;        // of the flush's number: which of the two epoch words it adds to
+    bool long_epoch = false;     // the running epoch is a long one
+#endif
 #ifdef RF_EXPERIMENT_SECTIONS
     unsigned long long sec_cache = 0, sec_steps = 0, sec_total = __builtin_readcyclecounter();
     FlushRecord rec;
@@ -2103,12 +2173,16 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
             W.step(p, G);
 #ifdef RF_EXPERIMENT_SECTIONS
             sec_steps++;
+            rec.wave_live = true;
             const unsigned long long e0 = __builtin_readcyclecounter();
 #endif
 
             const uint32_t lane = threadIdx.x & 63u;
             if (ballot(G.has) != 0ull) {
                 bool act = G.has;
+#ifdef RF_EXPERIMENT_SECTIONS
+                if (ballot(G.has && (G.row || G.pg_on)) != 0ull) rec.wave_lit = true;
+#endif
                 if (ballot(G.has && G.row) != 0ull) {
                     // lit wave-step: colour + density of every lane with a contribution
                     float v[A];
@@ -2188,28 +2262,84 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
             sec_cache += __builtin_readcyclecounter() - e0;
 #endif
         }
-        it++;
-        if ((it & (kEpoch - 1u)) == 0u) {
+        if (--left == 0u) {
 #ifdef RF_EXPERIMENT_SECTIONS
             const unsigned long long f0 = __builtin_readcyclecounter();
 #endif
+#if RF_EPOCH_WORD
+            uint32_t *const word = s_epoch + parity;
+            uint32_t extra = 0u;
+            const bool all_narrow = long_epoch;
+#else
+            uint32_t *const word = nullptr;
+            const uint32_t extra = 0u;
+            const bool all_narrow = false;
+#endif
+#if RF_EPOCH_FLAG_VOTE
+            // the vote rides on the epoch word; a block that turns out dead flushes what is left after the loop
+            __syncthreads();
+            if (ballot(W.alive) != 0ull) extra += kEpochAliveBit;
+            const bool flush_all = false;
+#else
             block_alive = __syncthreads_or(W.alive ? 1 : 0) != 0;
+            const bool flush_all = !block_alive;
+#endif
+#if RF_EPOCH_WORD
+            if (threadIdx.x == 0u) s_epoch[parity ^ 1u] = 0u;
+#endif
 #ifdef RF_EXPERIMENT_SECTIONS
+            if (rec.wave_lit) extra += kEpochLitBit;
             const unsigned long long f1 = __builtin_readcyclecounter();
-            cache_flush<NB>(s_rows, s_keys, s_touch, s_wide, !block_alive, p.attr_grad, p.points_grad, p.attr_pitch, rec);
+            cache_flush<NB>(s_rows, s_keys, s_touch, s_wide, flush_all, all_narrow, word, extra, p.attr_grad, p.points_grad, p.attr_pitch, rec);
             const unsigned long long f2 = __builtin_readcyclecounter();
 #else
-            cache_flush<NB>(s_rows, s_keys, s_touch, s_wide, !block_alive, p.attr_grad, p.points_grad, p.attr_pitch);
+            cache_flush<NB>(s_rows, s_keys, s_touch, s_wide, flush_all, all_narrow, word, extra, p.attr_grad, p.points_grad, p.attr_pitch);
 #endif
             __syncthreads();
+#if RF_EPOCH_WORD
+            const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)*word);
+            const uint32_t steps = epoch_steps(epoch_resident(w), epoch_any_wide(w));
+            long_epoch = steps != kEpoch;
+            left = steps;
+            parity ^= 1u;
+#if RF_EPOCH_FLAG_VOTE
+            block_alive = epoch_alive(w);
+#endif
+#else
+            left = kEpoch;
+#endif
 #ifdef RF_EXPERIMENT_SECTIONS
-            rec.arrive += f1 - f0;
-            rec.body += f2 - f1;
-            rec.close += __builtin_readcyclecounter() - f2;
-            rec.epochs++;
+            {
+                const unsigned long long d = f1 - f0, res = epoch_resident(w);
+                const bool lit = epoch_lit(w);
+                rec.arrive += d;
+                rec.body += f2 - f1;
+                rec.close += __builtin_readcyclecounter() - f2;
+                rec.epochs++;
+                if (rec.wave_live) {
+                    if (lit) rec.arr_live_lit += d, rec.n_live_lit++;
+                    else rec.arr_live_dens += d, rec.n_live_dens++;
+                } else {
+                    if (lit) rec.arr_done_lit += d, rec.n_done_lit++;
+                    else rec.arr_done_dens += d, rec.n_done_dens++;
+                }
+                if (lit) rec.res_sum_lit += res, rec.n_lit++, rec.res_max_lit = res > rec.res_max_lit ? res : rec.res_max_lit;
+                else rec.res_sum_dens += res, rec.n_dens++, rec.res_max_dens = res > rec.res_max_dens ? res : rec.res_max_dens;
+                if (long_epoch) rec.n_long++;
+                rec.wave_live = false;
+                rec.wave_lit = false;
+            }
 #endif
         }
     }
+#if RF_EPOCH_FLAG_VOTE
+    // every lane of the block is dead and the closing barrier is behind: each wave sends the rows its threads own
+#ifdef RF_EXPERIMENT_SECTIONS
+    cache_flush<NB>(s_rows, s_keys, s_touch, s_wide, true, false, nullptr, 0u, p.attr_grad, p.points_grad, p.attr_pitch, rec);
+#else
+    cache_flush<NB>(s_rows, s_keys, s_touch, s_wide, true, false, nullptr, 0u, p.attr_grad, p.points_grad, p.attr_pitch);
+#endif
+#endif
 #ifdef RF_EXPERIMENT_SECTIONS
     // wave clocks per section: [8] waiting for the hop's records + face hit, [9] backward_segment, [10] merge + cache
     // updates of the step, [11] barriers + flush of the epochs, [12] the whole walk, [13] wave-steps; of [11]:
@@ -2230,6 +2360,26 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
         atomicAdd(p.stats + 18, rec.wide);
         atomicAdd(p.stats + 19, rec.narrow);
         atomicAdd(p.stats + 20, rec.bypass);
+        // [14] and [17] split: the wave had a live lane in the epoch / had finished, in a lit / a density-only block-epoch
+        atomicAdd(p.stats + 21, rec.arr_live_lit);
+        atomicAdd(p.stats + 22, rec.arr_live_dens);
+        atomicAdd(p.stats + 23, rec.arr_done_lit);
+        atomicAdd(p.stats + 24, rec.arr_done_dens);
+        atomicAdd(p.stats + 25, rec.n_live_lit);
+        atomicAdd(p.stats + 26, rec.n_live_dens);
+        atomicAdd(p.stats + 27, rec.n_done_lit);
+        atomicAdd(p.stats + 28, rec.n_done_dens);
+        if (threadIdx.x == 0u) {
+            // per block: rows resident after the flush, sum [29] [30] and maximum [31] [32], block-epochs [33] [34],
+            // each lit / density-only, and [35] the long epochs begun
+            atomicAdd(p.stats + 29, rec.res_sum_lit);
+            atomicAdd(p.stats + 30, rec.res_sum_dens);
+            atomicMax(p.stats + 31, rec.res_max_lit);
+            atomicMax(p.stats + 32, rec.res_max_dens);
+            atomicAdd(p.stats + 33, rec.n_lit);
+            atomicAdd(p.stats + 34, rec.n_dens);
+            atomicAdd(p.stats + 35, rec.n_long);
+        }
     }
 #endif
 }

@@ -45,7 +45,7 @@ for _ in range(3):
     f = pipe.trace_forward(p, a, adj, off, rays, start)
     pipe.trace_backward(p, a, adj, off, rays, start, f["rgba"], g)
 torch.cuda.synchronize()
-stats = torch.zeros(24, dtype=torch.int64, device=dev)
+stats = torch.zeros(48, dtype=torch.int64, device=dev)   # the image backward writes slots 8..35
 pipe.experiment_stats = stats
 f = pipe.trace_forward(p, a, adj, off, rays, start)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -68,6 +68,16 @@ if workload != "train-batch" and s[17]:
              "evicted_wide_rows_per_block_epoch": round(s[18] / block_epochs, 2),
              "evicted_narrow_rows_per_block_epoch": round(s[19] / block_epochs, 2),
              "bypass_lane_adds_per_block_epoch": round(s[20] / block_epochs, 3), "bypass_lane_adds": s[20]}
+    # the first barrier's wait split two ways: the wave still had a live lane in the epoch (live) or had finished
+    # (done); the block added colour or point gradients in the epoch (lit) or density sums only (dens).  Shares of the
+    # walk's wave clocks, wave-epochs, and the rows resident after the flush per kind of block-epoch
+    kinds = ("live_lit", "live_dens", "done_lit", "done_dens")
+    flush["first_barrier_split"] = {k: {"share": round(s[21 + i] / tot, 4), "wave_epochs": s[25 + i],
+                                        "clocks_per_wave_epoch": round(s[21 + i] / max(s[25 + i], 1), 1)} for i, k in enumerate(kinds)}
+    flush["resident_rows_after_flush"] = {
+        "lit": {"block_epochs": s[33], "mean": round(s[29] / max(s[33], 1), 2), "max": s[31]},
+        "dens": {"block_epochs": s[34], "mean": round(s[30] / max(s[34], 1), 2), "max": s[32]}}
+    flush["long_block_epochs"] = s[35]
 print(json.dumps({"lib": os.path.basename(os.environ.get("RADFOAM_HIP_LIB", "libradfoam_hip.so")), "workload": workload, "sh_degree": sh, "empty_density": os.environ.get("EMPTY_DENSITY"), "backward_ms": round(e0.elapsed_time(e1), 3), "wave_steps": s[13],
                   "clocks_per_wave_step": round(tot / max(s[13], 1), 1),
                   "share_wait_records_and_face_hit": round(s[8] / tot, 3), "share_segment_colour_row_and_math": round(s[9] / tot, 3),
