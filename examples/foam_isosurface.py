@@ -6,16 +6,19 @@ colour carried to the vertices by ``vertex_t``, and Adam pulls the vertices onto
     loss = mean over the mesh's vertices of (|v - c| - r)^2,
 
 through ``mesh.vertices``, which carries autograd to the sites and to the densities.  The topology is extracted again every
-``--every`` steps; in between ``radfoam.isosurface_vertices`` re-evaluates the vertices of the last one, which costs one
-kernel and no triangulation.
+step: the triangulation is rebuilt incrementally, ``Triangulation.tets()`` reads the tetrahedra back off the new neighbour
+lists on the GPU (``radfoam.delaunay_tets``) and ``radfoam.isosurface`` runs over them.  With ``--every K`` only every
+K-th step does; in between ``radfoam.isosurface_vertices`` re-evaluates the vertices of the last topology, which costs one
+kernel and no triangulation.  The wall time of every step is printed.
 
-    python examples/foam_isosurface.py [--points 4000] [--steps 40] [--every 10] [--ply surface.ply]
+    python examples/foam_isosurface.py [--points 4000] [--steps 40] [--every 1] [--ply surface.ply]
 """
 from __future__ import annotations
 
 import argparse
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -56,10 +59,11 @@ def sphere_loss(vertices, centre, radius):
     return (((vertices - centre).norm(dim=1) - radius) ** 2).mean()
 
 
-def run(num_points=4000, steps=40, every=10, lr=2e-3, radius=0.6, level=0.5, seed=0, device="cuda:0", quiet=False,
+def run(num_points=4000, steps=40, every=1, lr=2e-3, radius=0.6, level=0.5, seed=0, device="cuda:0", quiet=False,
         ply=None):
-    """(loss, vertices, triangles, extracted) before every step and after the last one (steps + 1 tuples).  The density
-    starts as a bumpy ball, 1 at the centre and falling through ``level`` near |p| = ``radius``."""
+    """(loss, vertices, triangles, extracted, seconds) before every step and after the last one (steps + 1 tuples;
+    seconds: the wall time of the step, its extraction, loss, backward and update).  The density starts as a bumpy ball,
+    1 at the centre and falling through ``level`` near |p| = ``radius``."""
     dev = torch.device(device)
     gen = torch.Generator(device="cpu").manual_seed(seed)
     start = (torch.rand((num_points, 3), generator=gen) * 2.0 - 1.0).to(dev)
@@ -74,6 +78,9 @@ def run(num_points=4000, steps=40, every=10, lr=2e-3, radius=0.6, level=0.5, see
     opt = torch.optim.Adam([points, density], lr=lr)
     history, sites = [], None
     for step in range(steps + 1):
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        began = time.perf_counter()
         extract = step % every == 0 or step == steps
         if extract:
             if step:
@@ -83,17 +90,18 @@ def run(num_points=4000, steps=40, every=10, lr=2e-3, radius=0.6, level=0.5, see
         else:
             vertices = radfoam.isosurface_vertices(points, density, sites, level)       # the last topology, moved along
         loss = sphere_loss(vertices, centre, radius)
-        history.append((float(loss.detach()), vertices.size(0), triangles, extract))
+        if step < steps:
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        history.append((float(loss.detach()), vertices.size(0), triangles, extract, time.perf_counter() - began))
         if not quiet:
             print(f"step {step:3d}: loss {history[-1][0]:.6e}  vertices {history[-1][1]}  triangles {triangles}"
-                  + ("  (extracted)" if extract else ""))
-        if step == steps:
-            if ply:
-                write_ply(ply, mesh, vertex_colours(mesh, colours))
-            break
-        opt.zero_grad(set_to_none=True)
-        loss.backward()
-        opt.step()
+                  f"  {1e3 * history[-1][4]:.2f} ms" + ("  (extracted)" if extract else ""))
+        if step == steps and ply:
+            write_ply(ply, mesh, vertex_colours(mesh, colours))
     return history
 
 
@@ -101,13 +109,15 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--points", type=int, default=4000)
     ap.add_argument("--steps", type=int, default=40)
-    ap.add_argument("--every", type=int, default=10, help="extract the topology again every this many steps")
+    ap.add_argument("--every", type=int, default=1, help="extract the topology again every this many steps")
     ap.add_argument("--lr", type=float, default=2e-3)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ply", default=None, help="write the final mesh here")
     a = ap.parse_args()
     history = run(a.points, a.steps, a.every, a.lr, seed=a.seed, ply=a.ply)
-    print(f"sphere loss {history[0][0]:.6e} -> {history[-1][0]:.6e}")
+    extracting = sorted(h[4] for h in history[1:] if h[3])
+    print(f"sphere loss {history[0][0]:.6e} -> {history[-1][0]:.6e}; a step that extracts the topology: median "
+          f"{1e3 * extracting[len(extracting) // 2]:.2f} ms")
 
 
 if __name__ == "__main__":

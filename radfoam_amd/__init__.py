@@ -20,6 +20,7 @@ from .scene_ops import pack_attributes
 from .segments import (composite_entries, composite_segments, entry_weights, ray_distortion, ray_quantiles,
                        segment_points_grad, segment_rays_grad)
 from .sh_entries import sh_entries
+from .tets import DelaunayTets, delaunay_tets
 from .shims import (BatchFetcher, Triangulation, TriangulationFailedError, Viewer, build_aabb_tree,
                     farthest_neighbor, nn, run_with_viewer)
 
@@ -34,5 +35,5 @@ __all__ = [
     "differentiable_cell_moments", "BoxedCellGeometry", "cell_geometry_in_box",
     "cell_geometry_in_box_grad", "differentiable_cell_geometry_in_box", "BoxedCellMoments", "cell_moments_in_box",
     "cell_moments_in_box_grad", "differentiable_cell_moments_in_box", "face_area_in_box_grad", "IsoMesh", "isosurface",
-    "isosurface_vertices", "isosurface_vertices_grad",
+    "isosurface_vertices", "isosurface_vertices_grad", "DelaunayTets", "delaunay_tets",
 ]

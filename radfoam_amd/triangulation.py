@@ -13,14 +13,14 @@ finer than the coarsest coordinate of the same predicate to its grid -- inputs l
 triangulation (unmatched edges), not triangulated wrongly.
 
 No CPU path in this module: it needs the HIP library and CUDA (HIP) tensors.  The tetrahedra themselves
-(``tets()``, ``tet_adjacency()``, ``vert_to_tet()`` -- only the reference's viewer reads them) are not produced
-on the GPU; those three getters triangulate once more with Qhull on the host when asked.
+(``tets()``, ``tet_adjacency()``, ``vert_to_tet()`` -- the viewer and ``isosurface`` read them) come from the neighbour
+lists on the GPU when asked (radfoam_amd/tets.py: every row rebuilt into a star, the tetrahedra read off its link), in
+the reference's row order and with positively oriented rows; the result is kept until the next ``rebuild``.
 """
 from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
 import torch
 
 from . import _lib
@@ -158,7 +158,7 @@ class Triangulation:
         _check_points(points)
         self._n = -1
         self._adjacency = self._offsets = None
-        self._host = None
+        self._tets = None
         self.stats = {}
         self.rebuild(points, incremental=False)
 
@@ -181,7 +181,7 @@ class Triangulation:
         self._n = pts.size(0)
         self._points = sorted_pts.clone() if sorted_pts is pts else sorted_pts   # not the caller's (mutable) storage
         self._adjacency, self._offsets = adj, off
-        self._host = None
+        self._tets = None
         # whatever the tracer packed from the old lists is stale, even if a caller hands the new ones out at the old
         # addresses (the reference's from_blob getters do)
         from .pipeline import invalidate_caches
@@ -197,20 +197,18 @@ class Triangulation:
     def point_adjacency_offsets(self):
         return self._offsets
 
-    # the tetrahedra: not on the hot path (viewer only); Qhull on the host, on demand
-    def _host_mesh(self):
-        if self._host is None:
-            from scipy.spatial import Delaunay
-            self._host = Delaunay(self._points.cpu().numpy().astype(np.float64))
-        return self._host
+    # the tetrahedra: read back off the lists on demand (tets.py), kept until the next rebuild
+    def _mesh(self, adjacency=False):
+        if self._tets is None or (adjacency and self._tets.tet_adjacency is None):
+            from .tets import delaunay_tets
+            self._tets = delaunay_tets(self._points, self._adjacency, self._offsets, adjacency=adjacency)
+        return self._tets
 
     def tets(self):
-        return torch.from_numpy(self._host_mesh().simplices.astype(np.uint32)).to(self._points.device)
+        return self._mesh().tets
 
     def tet_adjacency(self):
-        t = self._host_mesh().neighbors.astype(np.int64).astype(np.uint32)
-        return torch.from_numpy(np.ascontiguousarray(t)).to(self._points.device)
+        return self._mesh(adjacency=True).tet_adjacency
 
     def vert_to_tet(self):
-        t = self._host_mesh().vertex_to_simplex.astype(np.uint32)
-        return torch.from_numpy(np.ascontiguousarray(t)).to(self._points.device)
+        return self._mesh().vert_to_tet
