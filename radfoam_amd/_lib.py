@@ -68,7 +68,7 @@ class LaunchOpts(C.Structure):
 # radfoam_hip_composite.h, radfoam_hip_distortion.h, radfoam_hip_quantiles.h, radfoam_hip_cell_reduce.h,
 # radfoam_hip_sh_entries.h, radfoam_hip_entry_weights.h, radfoam_hip_face_area_grad.h, radfoam_hip_mesh.h, radfoam_hip_moments.h,
 # radfoam_hip_moments_grad.h, radfoam_hip_box.h, radfoam_hip_box_grad.h, radfoam_hip_box_moments.h, radfoam_hip_box_area_grad.h
-# radfoam_hip_isosurface.h and radfoam_hip_tets.h declare:
+# radfoam_hip_isosurface.h, radfoam_hip_tets.h and radfoam_hip_locate.h declare:
 # name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -185,6 +185,9 @@ SYMBOLS = {
                                   _P, C.c_size_t, _P]),
     "rf_tets_match": (_INT, [_U32, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "rf_tets_pair_faces": (_INT, [_P, C.c_int64, _P, _P, _P, _P, _P]),
+    "rf_locate_walk": (_INT, [_P, _U32, _P, _P, _U32, _U32, _P, _P, _U32, _U32, _P, _P, _P, _P]),
+    "rf_interpolate": (_INT, [_P, _U32, _P, _U32, _U32, _P, _U32, _P, _P, _U32, _P, _P, _P, _P]),
+    "rf_interpolate_grad": (_INT, [_P, _U32, _P, _U32, _U32, _P, _U32, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -158,7 +158,7 @@ class Triangulation:
         _check_points(points)
         self._n = -1
         self._adjacency = self._offsets = None
-        self._tets = None
+        self._tets = self._tree = None
         self.stats = {}
         self.rebuild(points, incremental=False)
 
@@ -181,7 +181,7 @@ class Triangulation:
         self._n = pts.size(0)
         self._points = sorted_pts.clone() if sorted_pts is pts else sorted_pts   # not the caller's (mutable) storage
         self._adjacency, self._offsets = adj, off
-        self._tets = None
+        self._tets = self._tree = None
         # whatever the tracer packed from the old lists is stale, even if a caller hands the new ones out at the old
         # addresses (the reference's from_blob getters do)
         from .pipeline import invalidate_caches
@@ -212,3 +212,20 @@ class Triangulation:
 
     def vert_to_tet(self):
         return self._mesh().vert_to_tet
+
+    def locate(self, queries: torch.Tensor):
+        """TetLocation(tet int64[...], hops int32[...]) of float32 CUDA ``queries`` [...,3] in ``tets()``
+        (radfoam.locate_tets): every walk starts at ``vert_to_tet()`` of the site nearest to its query, found through the
+        AABB tree of the kd-ordered points (nearest_point_tree).  The tree is built on the first call and kept, with the
+        tetrahedra, until the next rebuild."""
+        from .locate import locate_tets
+        from .scene_ops import nearest_point_tree
+        mesh = self._mesh(adjacency=True)
+        if self._tree is None:
+            self._tree = build_aabb_tree(self._points)
+        q = queries.detach()
+        finite = torch.isfinite(q).all(-1, keepdim=True)               # such a query is not walked: any start will do
+        nearest = nearest_point_tree(self._points, self._tree, torch.where(finite, q, torch.zeros_like(q)))
+        nearest = nearest.view(torch.int32).to(torch.int64).clamp(0, self._n - 1)
+        start = mesh.vert_to_tet.view(torch.int32)[nearest]
+        return locate_tets(self._points, mesh.tets, mesh.tet_adjacency, queries, start=start)
