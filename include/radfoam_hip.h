@@ -68,7 +68,11 @@ typedef struct rf_launch_opts {
     uint32_t backward_mode;   /* rf_trace_backward only: 0 = auto, 1 = per-lane atomics, 2 = wave     */
                               /*   pre-reduced atomics, 3 = block-level LDS write-combining, 4 =      */
                               /*   direct row-coalesced atomics (3, 4 need the trail and fall back to */
-                              /*   2 without it; auto = 3 for image-shaped batches, 4 for flat ones)  */
+                              /*   2 without it; auto = 3 for image-shaped batches, 4 for flat ones), */
+                              /*   5 = mode 3 with the full backward functor on every segment: mode 3 */
+                              /*   keeps, per ray, dL/dalpha of its last segment through a cell of    */
+                              /*   density exactly 0 and reuses it while the ray stays in such cells  */
+                              /*   (same floats per contribution); 5 never does, for tests and A/B    */
     uint64_t *stats;          /* optional device uint64[8]: walk counters for the roofline figure     */
                               /*   [0] cells scanned [1] faces scanned [2] hops [3] segments          */
                               /*   [4] lit segments; accumulated with atomics, caller zeroes          */

@@ -114,6 +114,8 @@ struct BwdParams {
     const uint32_t *trail_hops;
     uint32_t trail_cap, trail_slots;
     uint32_t attr_pitch;         // floats between two rows of attr_grad (>= A; rf_launch_opts.attr_grad_pitch)
+    uint32_t empty_memo;         // image replay: 1 = the empty-run memo may become valid (TrailWalker::step); 0 = the full
+                                 // functor on every segment (backward_mode 5, or point_error given)
     unsigned long long *stats;   // optional scatter counters (experiments): [0] row flushes [1] values flushed
                                  // [2] lane contributions that bypassed the block cache [3] cached lane contributions
 };
@@ -1429,10 +1431,13 @@ __device__ __forceinline__ void init_backward_ray(BwdRay &R) {
 // PAIRS: the four bisector gradients as two shared evaluations (bisector_grad_pair) -- the same floats; worth it where
 // registers are to spare (flat-batch replay: 4.47 -> 4.40 ms, every segment lit 11.98 -> 11.76), a loss where they are not
 // (image replay at its 128-VGPR limit: 3.77 -> 3.99 ms, the shared values spill; profiles/r05/e_bisector_pairs_ab.log)
+// memo / memo_ok (the trail replay's empty-run memo, TrailWalker): dL/dalpha of this segment, and whether the segment
+// left the ray as it found it -- density exactly 0 and the bisector block skipped, so that T, C and the quantile state
+// are unchanged and the next segment through such a cell computes the same dL/dalpha again, bit for bit.
 template <int DEG, bool HALF, bool QUANT = true, bool PAIRS = false>
 __device__ __forceinline__ bool backward_segment(const BwdParams &p, BwdRay &R, const float (&sh)[sh_dim(DEG)],
                                                  uint32_t cur, float4 head, float4 nhead, float t1,
-                                                 StepGrad &G) {
+                                                 StepGrad &G, float &memo, bool &memo_ok) {
     const FoamView &fv = p.foam;
     const uint32_t nq = QUANT ? p.nq : 0u;
     const float t0 = R.t0;
@@ -1485,6 +1490,7 @@ __device__ __forceinline__ bool backward_segment(const BwdParams &p, BwdRay &R, 
     // The four bisector gradients only enter through dL_dt0 / dL_dt1; both are exactly zero in a
     // cell of density 0 (83 % of the segments of the benchmark scene), where the block is skipped.
     // (Differs from the reference only if a bisector gradient is non-finite there: 0 * inf.)
+    memo = dL_da;
     if (dL_dt0 != 0.0f || dL_dt1 != 0.0f) {
         float ax = 0.0f, ay = 0.0f, az = 0.0f;  // dt0_dprev
         float bx, by, bz;                        // dt1_dcurrent
@@ -1515,6 +1521,9 @@ __device__ __forceinline__ bool backward_segment(const BwdParams &p, BwdRay &R, 
         R.ngx = fma_(dL_dt1, fx, R.ngx);
         R.ngy = fma_(dL_dt1, fy, R.ngy);
         R.ngz = fma_(dL_dt1, fz, R.ngz);
+        memo_ok = false;
+    } else {
+        memo_ok = s == 0.0f;
     }
 
     // what the reference adds with atomics at this point (pipeline.cu:305-328): prev_point_grad ->
@@ -1548,6 +1557,51 @@ __device__ __forceinline__ bool backward_segment(const BwdParams &p, BwdRay &R, 
     R.ngx = R.ngy = R.ngz = 0.0f;
     R.T = Tn;
     return Tn > p.settings.weight_threshold;
+}
+
+template <int DEG, bool HALF, bool QUANT = true, bool PAIRS = false>
+__device__ __forceinline__ bool backward_segment(const BwdParams &p, BwdRay &R, const float (&sh)[sh_dim(DEG)],
+                                                 uint32_t cur, float4 head, float4 nhead, float t1,
+                                                 StepGrad &G) {
+    float memo = 0.0f;
+    bool memo_ok;
+    return backward_segment<DEG, HALF, QUANT, PAIRS>(p, R, sh, cur, head, nhead, t1, G, memo, memo_ok);
+}
+
+// What backward_segment leaves behind for a segment through a cell of density exactly 0 whose ray carries a valid memo
+// (TrailWalker): alpha = w = 0, T and C as they were, no colour row, the bisector block skipped, and
+// dL/ds = dL/dalpha * dt with the dL/dalpha of the ray's previous such segment.  The same floats, without the
+// exponential, the divides and the dot products.
+template <bool QUANT>
+__device__ __forceinline__ void backward_segment_empty(const BwdParams &p, BwdRay &R, uint32_t cur, float4 head, float t1,
+                                                       float memo, StepGrad &G) {
+    const float dt = __builtin_fmaxf(t1 - R.t0, 0.0f);
+    float dL_ds = memo * dt;
+    if constexpr (QUANT) {
+        if (R.qi < p.nq) dL_ds = fma_(-dt, R.cdg, dL_ds);
+    }
+    G.has = true;
+    G.cur = cur;
+    G.prev = R.prev;
+    G.px = R.pgx;
+    G.py = R.pgy;
+    G.pz = R.pgz;
+    G.pg_on = (R.prev != kNone) && (R.pgx != 0.0f || R.pgy != 0.0f || R.pgz != 0.0f);
+    G.dLr = G.dLg = G.dLb = 0.0f;
+    G.dL_ds = dL_ds;
+    G.row = false;
+
+    R.ppx = head.x;
+    R.ppy = head.y;
+    R.ppz = head.z;
+    R.prev = cur;
+    R.pgx = R.cgx;
+    R.pgy = R.cgy;
+    R.pgz = R.cgz;
+    R.cgx = R.ngx;
+    R.cgy = R.ngy;
+    R.cgz = R.ngz;
+    R.ngx = R.ngy = R.ngz = 0.0f;
 }
 
 __device__ __forceinline__ void clear_step(StepGrad &G) {
@@ -2015,10 +2069,13 @@ __device__ __forceinline__ void cache_flush(double *rows, uint32_t *keys, uint8_
 // The per-lane state of a trail replay and one hop of it, shared by the replay kernels below.
 // Pipeline registers: id1 = trail[i+1], id0 = trail[i], q0 = cells[id0]; every call of step()
 // issues the loads of hop i+1 / i+2 first and then computes hop i from registers.
-template <int DEG, bool HALF, bool QUANT, bool PAIRS = false>
+// MEMO: the empty-run memo of step() (the image replay; the flat replays are compiled without it).
+template <int DEG, bool HALF, bool QUANT, bool PAIRS = false, bool MEMO = false>
 struct TrailWalker {
     static constexpr int NB = sh_dim(DEG);
     BwdRay R;
+    float memo = 0.0f;                    // dL/dalpha of the lane's last segment through the full functor
+    unsigned long long memo_ok = 0ull;    // wave mask (scalar registers, as ScanState::b0/b1): lanes whose memo is valid
     float sh[NB];
     float4 head, q0;
     uint32_t cur, hops, recorded, i, n, id0, id1, slot;
@@ -2028,6 +2085,9 @@ struct TrailWalker {
     bool alive;
 #ifdef RF_EXPERIMENT_SECTIONS
     unsigned long long sec_wait = 0, sec_segment = 0;   // wave clocks: until the hop's records are there / in backward_segment
+    // sec_segment's part in "empty" wave-steps (every lane with a segment is in a cell of density exactly 0), and the
+    // wave-steps: empty ones, those of them that took backward_segment_empty, and those without any segment
+    unsigned long long sec_segment_empty = 0, steps_empty = 0, steps_fast = 0, steps_no_segment = 0;
 #endif
 
     __device__ __forceinline__ void init(const BwdParams &p) {
@@ -2065,7 +2125,10 @@ struct TrailWalker {
 #ifdef RF_EXPERIMENT_SECTIONS
         const unsigned long long c0 = __builtin_readcyclecounter();
 #endif
-        if (alive) {
+        if constexpr (MEMO) {
+            // a live lane's n equals its i: both count its steps.  One counter instead of two makes room for the memo
+            if (alive && i >= p.settings.max_intersections) alive = false;
+        } else if (alive) {
             n++;
             if (n > p.settings.max_intersections) alive = false;
         }
@@ -2091,9 +2154,35 @@ struct TrailWalker {
         const unsigned long long c1 = __builtin_readcyclecounter();
         sec_wait += c1 - c0;
 #endif
+        // The empty-run memo.  Through a cell of density exactly 0 the functor changes neither T nor C, so every
+        // segment of an empty run after the first computes the first one's dL/dalpha again, bit for bit.  A wave-step in
+        // which every lane with a segment is in such a cell and holds a valid memo takes backward_segment_empty; any
+        // other wave-step runs the full functor in every lane (the choice is wave-uniform: a divergent fast path would
+        // issue both sides).  A lane's memo becomes valid when the full functor ran on a density-0 segment and skipped
+        // the bisector block (dL/dalpha finite), and invalid when it ran on anything else.  A segment that ends at
+        // t1 = inf makes alpha NaN in the functor and is left to it.  With point_error the functor adds w * err = +0 to
+        // it per segment; that launch never takes the fast path (p.empty_memo is cleared on the host).
+        const bool seg = alive && t1 > R.t0;
+        bool fast = false, seg_ok = false;
+        if constexpr (MEMO) {
+            const unsigned long long segs = ballot(seg);
+            const unsigned long long full = ballot(seg && !(head.w == 0.0f && t1 < __builtin_inff()));
+            fast = ((segs & ~memo_ok) | full) == 0ull;
+        }
+#ifdef RF_EXPERIMENT_SECTIONS
+        // a wave-step is "empty" when it has a segment and every lane that has one is in a cell of density exactly 0
+        const bool step_empty = ballot(seg) != 0ull && ballot(seg && head.w != 0.0f) == 0ull;
+        if (ballot(seg) == 0ull) steps_no_segment++;
+#endif
         if (alive) {
-            if (t1 > R.t0) {
-                if (!backward_segment<DEG, HALF, QUANT, PAIRS>(p, R, sh, cur, head, nhead, t1, G)) alive = false;
+            if (seg) {
+                if (MEMO && fast) {
+                    backward_segment_empty<QUANT>(p, R, cur, head, t1, memo, G);
+                } else {
+                    bool ok;
+                    if (!backward_segment<DEG, HALF, QUANT, PAIRS>(p, R, sh, cur, head, nhead, t1, G, memo, ok)) alive = false;
+                    if constexpr (MEMO) seg_ok = ok;
+                }
             }
 #ifdef RF_EXPERIMENT_SECTIONS
             asm volatile("" : "+v"(G.dL_ds));
@@ -2103,14 +2192,36 @@ struct TrailWalker {
             head = nhead;
             i++;
         }
+        if constexpr (MEMO) {
+            if (!fast) memo_ok = (memo_ok & ~ballot(seg)) | (p.empty_memo ? ballot(seg && seg_ok) : 0ull);
+        }
 #ifdef RF_EXPERIMENT_SECTIONS
-        sec_segment += __builtin_readcyclecounter() - c1;
+        {
+            const unsigned long long c2 = __builtin_readcyclecounter();
+            sec_segment += c2 - c1;
+            if (step_empty) sec_segment_empty += c2 - c1, steps_empty++;
+            if (MEMO && fast && step_empty) steps_fast++;
+        }
 #endif
         id0 = id1;
         id1 = id2;
         q0 = q1;
     }
 };
+
+// The empty-run memo of the image replay (TrailWalker::step; profiles/r09/b_image_backward_memo_ab.log).
+// -DRF_BWD_EMPTY_MEMO=0 compiles every instance without it.
+#ifndef RF_BWD_EMPTY_MEMO
+#define RF_BWD_EMPTY_MEMO 1
+#endif
+// An instance that spills more with the memo stays on the full functor (profiles/r09/c_image_backward_resources_before_after.txt):
+// every instance with depth quantiles (SH 2 fp32: 68 -> 88 bytes of scratch), SH 3 without them (fp32 120 -> 148 bytes, and
+// its backward 6.03-6.11 -> 6.47 ms in the log above; fp16 132 -> 136) and SH 1 fp16 (20 -> 28).  The benchmark's SH 2 fp32
+// instance goes from 0 to 12 bytes and is faster with it, which is what the log is about.  So: SH 0 and SH 2 in fp32 and
+// fp16, SH 1 in fp32, without quantiles.
+constexpr bool empty_memo_instance(int deg, bool half, bool quant) {
+    return RF_BWD_EMPTY_MEMO != 0 && !quant && deg <= 2 && !(deg == 1 && half);
+}
 
 template <int DEG, bool HALF, bool QUANT>
 __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)) void backward_replay_cached_kernel(BwdParams p) {
@@ -2142,7 +2253,7 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
     }
     __syncthreads();
 
-    TrailWalker<DEG, HALF, QUANT> W;
+    TrailWalker<DEG, HALF, QUANT, false, empty_memo_instance(DEG, HALF, QUANT)> W;
     W.init(p);
     const float (&sh)[NB] = W.sh;
 
@@ -2380,6 +2491,13 @@ __global__ __launch_bounds__(kBlock, (DEG <= 2 ? RF_BWD_WAVES : RF_BWD_WAVES_D3)
             atomicAdd(p.stats + 34, rec.n_dens);
             atomicAdd(p.stats + 35, rec.n_long);
         }
+        // of [9] and [13]: [36] backward_segment's clocks in wave-steps whose every lane with a segment is in a cell of
+        // density exactly 0, [37] those wave-steps, [38] those of them that took the empty-run memo's path, [39] the
+        // wave-steps without any segment
+        atomicAdd(p.stats + 36, W.sec_segment_empty);
+        atomicAdd(p.stats + 37, W.steps_empty);
+        atomicAdd(p.stats + 38, W.steps_fast);
+        atomicAdd(p.stats + 39, W.steps_no_segment);
     }
 #endif
 }
@@ -3435,8 +3553,8 @@ int rf_trace_backward(int sh_degree, int attr_type, const rf_trace_settings *set
         return fail(RF_ERR_INVALID_ARGUMENT, "rf_trace_backward: null pointer");
     if (num_depth_quantiles && depth_quantiles && (!quantile_point_indices || !depth_grad))
         return fail(RF_ERR_INVALID_ARGUMENT, "depth_grad must be provided if depth_quantiles is provided");
-    if (opts->backward_mode > 4u)
-        return fail(RF_ERR_INVALID_ARGUMENT, "rf_trace_backward: backward_mode must be 0..4");
+    if (opts->backward_mode > 5u)
+        return fail(RF_ERR_INVALID_ARGUMENT, "rf_trace_backward: backward_mode must be 0..5");
     if (opts->forward_mode > 5u) return fail(RF_ERR_INVALID_ARGUMENT, "rf_trace_backward: forward_mode must be 0..5");
     const bool half = attr_type == RF_ATTR_FLOAT16;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -3483,6 +3601,10 @@ int rf_trace_backward(int sh_degree, int attr_type, const rf_trace_settings *set
     // 0 = auto: with a trail to replay, the block cache for image-shaped batches (dense: many rays per
     // cell and tile) and direct row atomics for flat ones; wave-reduced scatter without a trail
     int mode = (int)opts->backward_mode;
+    // 5 = 3 with the full functor on every segment; point_error receives an add per segment, which the memo's path
+    // does not make, so a launch with point_error runs without the memo as well
+    p.empty_memo = (mode != 5 && !p.point_error) ? 1u : 0u;
+    if (mode == 5) mode = 3;
     if (mode == 0) mode = p.trail ? (p.grid.img_w ? 3 : 4) : 2;
     if ((mode == 3 || mode == 4) && !p.trail) mode = 2;
     return dispatch<LaunchBackward>(sh_degree, half, p, mode, s);

@@ -234,8 +234,8 @@ class Pipeline:
         self._cache = _FoamCache()
         #: reuse the packed foam between calls while the inputs are unchanged
         self.cache_foam = True
-        #: 0 auto, 1 per-lane atomics, 2 wave pre-reduced atomics, 3 block cache, 4 direct row atomics
-        #: (rf_launch_opts.backward_mode)
+        #: 0 auto, 1 per-lane atomics, 2 wave pre-reduced atomics, 3 block cache, 4 direct row atomics, 5 = 3 with the
+        #: full functor on every segment (no empty-run memo; tests and A/B) (rf_launch_opts.backward_mode)
         self.backward_mode = 0
         #: how the scans of a launch are scheduled (rf_launch_opts.forward_mode); every mode returns the same results bit
         #: for bit -- the reference's scan, tracing_utils.cuh:43-67.  0 auto, 1 face blocks requested one at a time, 2 the

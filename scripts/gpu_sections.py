@@ -45,7 +45,7 @@ for _ in range(3):
     f = pipe.trace_forward(p, a, adj, off, rays, start)
     pipe.trace_backward(p, a, adj, off, rays, start, f["rgba"], g)
 torch.cuda.synchronize()
-stats = torch.zeros(48, dtype=torch.int64, device=dev)   # the image backward writes slots 8..35
+stats = torch.zeros(48, dtype=torch.int64, device=dev)   # the image backward writes slots 8..39
 pipe.experiment_stats = stats
 f = pipe.trace_forward(p, a, adj, off, rays, start)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -78,6 +78,15 @@ if workload != "train-batch" and s[17]:
         "lit": {"block_epochs": s[33], "mean": round(s[29] / max(s[33], 1), 2), "max": s[31]},
         "dens": {"block_epochs": s[34], "mean": round(s[30] / max(s[34], 1), 2), "max": s[32]}}
     flush["long_block_epochs"] = s[35]
+    # the segment section split by the kind of wave-step: "all_empty" = every lane that has a segment is in a cell of
+    # density exactly 0 (what the empty-run memo can serve), "other" = the rest (wave-steps without any segment
+    # included); took_memo_path = the all-empty wave-steps that skipped the functor (0 in a build without the memo)
+    flush["segment_split"] = {
+        "all_empty": {"wave_steps": s[37], "share_of_walk": round(s[36] / tot, 4), "share_of_segment_section": round(s[36] / max(s[9], 1), 4),
+                      "clocks_per_wave_step": round(s[36] / max(s[37], 1), 1), "took_memo_path": s[38]},
+        "other": {"wave_steps": s[13] - s[37], "share_of_walk": round((s[9] - s[36]) / tot, 4),
+                  "share_of_segment_section": round((s[9] - s[36]) / max(s[9], 1), 4),
+                  "clocks_per_wave_step": round((s[9] - s[36]) / max(s[13] - s[37], 1), 1), "without_any_segment": s[39]}}
 print(json.dumps({"lib": os.path.basename(os.environ.get("RADFOAM_HIP_LIB", "libradfoam_hip.so")), "workload": workload, "sh_degree": sh, "empty_density": os.environ.get("EMPTY_DENSITY"), "backward_ms": round(e0.elapsed_time(e1), 3), "wave_steps": s[13],
                   "clocks_per_wave_step": round(tot / max(s[13], 1), 1),
                   "share_wait_records_and_face_hit": round(s[8] / tot, 3), "share_segment_colour_row_and_math": round(s[9] / tot, 3),
