@@ -208,7 +208,10 @@ def trace_paths(sh_degree, points, attributes, adjacency, offsets, rays, start_p
 def trace_backward(sh_degree, points, attributes, adjacency, offsets, rays, start_point,
                    rgb_out, grad_in, depth_quantiles=None, depth_indices=None, depth_grad_in=None,
                    ray_error=None, weight_threshold=None, max_intersections=None, diff=None,
-                   strict=True, num_threads=0):
+                   strict=True, num_threads=0, return_magnitude=False):
+    """return_magnitude=True adds ``points_grad_mag`` [N,3], ``attr_grad_mag`` [N,A] and (with ray_error)
+    ``point_error_mag`` [N,1], float64: per element, the sum of |v| over every v the walk adds into it.  The gradients
+    themselves are bit for bit what the default call returns."""
     attr_half = attributes.dtype == np.float16
     adt = np.float16 if attr_half else np.float32
     points = _c(points, np.float32)
@@ -235,7 +238,7 @@ def trace_backward(sh_degree, points, attributes, adjacency, offsets, rays, star
     ag = np.zeros((n, a), dtype=adt)
     pe = np.zeros((n, 1), dtype=adt) if re is not None else None
     diff = _c(diff, np.uint16) if diff is not None else None
-    lib().rfo_trace_backward(
+    call = (
         C.c_int(sh_degree), C.c_int(int(attr_half)), _settings(weight_threshold, max_intersections),
         C.c_uint32(n), _p(points), _p(attributes), C.c_uint32(adjacency.shape[0]), _p(adjacency),
         _p(offsets), _p(diff), C.c_uint32(r), _p(rays), _p(start_point), C.c_uint32(nq), _p(q),
@@ -244,6 +247,17 @@ def trace_backward(sh_degree, points, attributes, adjacency, offsets, rays, star
     out = {"points_grad": pg, "attr_grad": ag}
     if pe is not None:
         out["point_error"] = pe
+    if return_magnitude:
+        pgm = np.zeros((n, 3), dtype=np.float64)
+        agm = np.zeros((n, a), dtype=np.float64)
+        pem = np.zeros((n, 1), dtype=np.float64) if pe is not None else None
+        lib().rfo_trace_backward_mag(*call, _p(pgm), _p(agm), _p(pem))
+        out["points_grad_mag"] = pgm
+        out["attr_grad_mag"] = agm
+        if pem is not None:
+            out["point_error_mag"] = pem
+    else:
+        lib().rfo_trace_backward(*call)
     return out
 
 

@@ -212,12 +212,16 @@ static float rf_logf(float x) {
 typedef struct {
     uint32_t *keys;      /* cap entries; RFO_NONE = empty */
     float *rows;         /* cap x width */
+    double *mrows;       /* cap x width: sum of |addend| per element of rows, or NULL (rfo_trace_backward_mag) */
     uint32_t cap, used, width;
     int A;
     float *pg, *ag, *pe; /* the shared outputs the table is merged into (pe may be NULL) */
+    double *mag;         /* shadow of the outputs, laid out [pg | ag | pe] over num_points cells, or NULL */
+    size_t num_points;
 } rfo_wc_t;
 
-static void rfo_wc_init(rfo_wc_t *t, uint32_t cap, int A, float *pg, float *ag, float *pe) {
+static void rfo_wc_init(rfo_wc_t *t, uint32_t cap, int A, float *pg, float *ag, float *pe, double *mag,
+                        size_t num_points) {
     t->cap = cap;
     t->used = 0;
     t->width = (uint32_t)A + 4u;
@@ -227,6 +231,9 @@ static void rfo_wc_init(rfo_wc_t *t, uint32_t cap, int A, float *pg, float *ag, 
     t->pe = pe;
     t->keys = (uint32_t *)malloc(sizeof(uint32_t) * cap);
     t->rows = (float *)calloc((size_t)cap * t->width, sizeof(float));
+    t->mag = mag;
+    t->num_points = num_points;
+    t->mrows = mag ? (double *)calloc((size_t)cap * t->width, sizeof(double)) : NULL;
     memset(t->keys, 0xFF, sizeof(uint32_t) * cap);
 }
 
@@ -250,6 +257,27 @@ static void rfo_wc_flush(rfo_wc_t *t) {
             t->pe[cell] += row[3 + t->A];
         }
         memset(row, 0, sizeof(float) * t->width);
+        if (t->mrows) {     /* the same merge for the shadow: [3 | A | 1] of the row into [pg | ag | pe] of the outputs */
+            double *mrow = t->mrows + (size_t)e * t->width;
+            double *mpg = t->mag + 3 * (size_t)cell;
+            double *mag_ag = t->mag + 3 * t->num_points + (size_t)cell * t->A;
+            double *mpe = t->mag + (3 + (size_t)t->A) * t->num_points + cell;
+            for (int i = 0; i < 3; ++i)
+                if (mrow[i] != 0.0) {
+#pragma omp atomic
+                    mpg[i] += mrow[i];
+                }
+            for (int i = 0; i < t->A; ++i)
+                if (mrow[3 + i] != 0.0) {
+#pragma omp atomic
+                    mag_ag[i] += mrow[3 + i];
+                }
+            if (t->pe && mrow[3 + t->A] != 0.0) {
+#pragma omp atomic
+                *mpe += mrow[3 + t->A];
+            }
+            memset(mrow, 0, sizeof(double) * t->width);
+        }
         t->keys[e] = RFO_NONE;
     }
     t->used = 0;
@@ -276,6 +304,7 @@ static inline float *rfo_wc_row(rfo_wc_t *t, uint32_t cell) {
 static void rfo_wc_free(rfo_wc_t *t) {
     free(t->keys);
     free(t->rows);
+    free(t->mrows);
 }
 
 /* ------------------------------------------------------------------------------------ */
@@ -468,14 +497,21 @@ void rfo_trace_paths(int sh_degree, rfo_settings settings, uint32_t num_points, 
     }
 }
 
-void rfo_trace_backward(int sh_degree, int attr_half, rfo_settings settings, uint32_t num_points,
-                        const float *points, const void *attributes, uint32_t adj_size,
-                        const uint32_t *adj, const uint32_t *offsets, const uint16_t *diff,
-                        uint32_t num_rays, const float *rays, const uint32_t *start, uint32_t nq,
-                        const float *quantiles, const uint32_t *qidx, const void *rgba,
-                        const void *rgba_grad, const float *depth_grad, const void *ray_error,
-                        float *points_grad, void *attr_grad, void *point_error, int strict,
-                        int num_threads) {
+/* rfo_trace_backward_mag: the same, and -- where points_grad_mag is not NULL -- the MAGNITUDE of every gradient element:
+ * points_grad_mag[N,3], attr_grad_mag[N,A], point_error_mag[N] (double; the last only with point_error) receive the
+ * sum of |v| over every v the walk adds into that element, the scale against which a difference in rounding or in the
+ * order of the sum is measured (tests/helpers.py: grad_close_elements).  The shadow sums travel
+ * the way the values do (directly with one thread, through the write-combining tables with several) and never touch
+ * the values: the gradients are bit for bit those of rfo_trace_backward. */
+void rfo_trace_backward_mag(int sh_degree, int attr_half, rfo_settings settings, uint32_t num_points,
+                            const float *points, const void *attributes, uint32_t adj_size,
+                            const uint32_t *adj, const uint32_t *offsets, const uint16_t *diff,
+                            uint32_t num_rays, const float *rays, const uint32_t *start, uint32_t nq,
+                            const float *quantiles, const uint32_t *qidx, const void *rgba,
+                            const void *rgba_grad, const float *depth_grad, const void *ray_error,
+                            float *points_grad, void *attr_grad, void *point_error, int strict,
+                            int num_threads, double *points_grad_mag, double *attr_grad_mag,
+                            double *point_error_mag) {
     int A = 1 + 3 * (sh_degree + 1) * (sh_degree + 1);
     float *attr_f = NULL, *rgba_f = NULL, *g_f = NULL, *err_f = NULL;
     uint16_t *diff_own = NULL;
@@ -504,13 +540,16 @@ void rfo_trace_backward(int sh_degree, int attr_half, rfo_settings settings, uin
     float *pg = tl;
     float *ag = pg + (size_t)num_points * 3;
     float *pe = ag + (size_t)num_points * A;
+    double *mag = points_grad_mag ? (double *)calloc(per ? per : 1, sizeof(double)) : NULL;
 #pragma omp parallel num_threads(nt)
     {
         rfo_wc_t table;
-        sink_t_f32 sink = {pg, ag, point_error ? pe : NULL, 0, NULL};
+        sink_t_f32 sink = {pg, ag, point_error ? pe : NULL, 0, NULL, tl, mag};
         if (nt > 1) {
-            rfo_wc_init(&table, 1u << 15, A, pg, ag, point_error ? pe : NULL);
+            rfo_wc_init(&table, 1u << 15, A, pg, ag, point_error ? pe : NULL, mag, num_points);
             sink.wc = &table;
+            sink.base = table.rows;
+            sink.mag_base = table.mrows;
         }
 #pragma omp for schedule(dynamic, 64)
         for (int64_t r = 0; r < (int64_t)num_rays; ++r) {
@@ -529,12 +568,32 @@ void rfo_trace_backward(int sh_degree, int attr_half, rfo_settings settings, uin
     for (size_t i = 0; i < (size_t)num_points * A; ++i) store_attr(attr_grad, i, ag[i], attr_half);
     if (point_error)
         for (size_t i = 0; i < num_points; ++i) store_attr(point_error, i, pe[i], attr_half);
+    if (mag) {
+        memcpy(points_grad_mag, mag, sizeof(double) * 3 * (size_t)num_points);
+        memcpy(attr_grad_mag, mag + 3 * (size_t)num_points, sizeof(double) * (size_t)A * num_points);
+        if (point_error && point_error_mag)
+            memcpy(point_error_mag, mag + (3 + (size_t)A) * num_points, sizeof(double) * (size_t)num_points);
+    }
+    free(mag);
     free(tl);
     free(attr_f);
     free(rgba_f);
     free(g_f);
     free(err_f);
     free(diff_own);
+}
+
+void rfo_trace_backward(int sh_degree, int attr_half, rfo_settings settings, uint32_t num_points,
+                        const float *points, const void *attributes, uint32_t adj_size,
+                        const uint32_t *adj, const uint32_t *offsets, const uint16_t *diff,
+                        uint32_t num_rays, const float *rays, const uint32_t *start, uint32_t nq,
+                        const float *quantiles, const uint32_t *qidx, const void *rgba,
+                        const void *rgba_grad, const float *depth_grad, const void *ray_error,
+                        float *points_grad, void *attr_grad, void *point_error, int strict,
+                        int num_threads) {
+    rfo_trace_backward_mag(sh_degree, attr_half, settings, num_points, points, attributes, adj_size, adj, offsets, diff,
+                           num_rays, rays, start, nq, quantiles, qidx, rgba, rgba_grad, depth_grad, ray_error,
+                           points_grad, attr_grad, point_error, strict, num_threads, NULL, NULL, NULL);
 }
 
 /* camera by value, as the reference's Camera struct      src/tracing/camera.h:17-26 */
@@ -669,7 +728,7 @@ void rfo_trace_backward_f64(int sh_degree, rfo_settings settings, uint32_t num_p
     memset(points_grad, 0, sizeof(double) * 3 * (size_t)num_points);
     memset(attr_grad, 0, sizeof(double) * (size_t)A * num_points);
     if (point_error) memset(point_error, 0, sizeof(double) * (size_t)num_points);
-    sink_t_f64 sink = {points_grad, attr_grad, point_error, 0, NULL};
+    sink_t_f64 sink = {points_grad, attr_grad, point_error, 0, NULL, NULL, NULL};
     for (uint32_t r = 0; r < num_rays; ++r) {
         backward_ray_f64(&fm, rays + 6 * (size_t)r, start[r], nq,
                          quantiles ? quantiles + (size_t)r * nq : NULL,

@@ -34,7 +34,27 @@ typedef struct {
     REAL *pg, *ag, *pe;
     int atomic;
     void *wc;
+    /* optional magnitude shadow (rfo_trace_backward_mag): mag_base mirrors, element for element, the block of REALs that
+     * starts at base -- the output arrays laid out [pg | ag | pe], or the rows of the write-combining table -- and receives
+     * |v| in double for every v added there.  NULL: no shadow, and nothing below touches it. */
+    const REAL *base;
+    double *mag_base;
 } SUF(sink_t);
+
+/* a gradient add: the value as ever, and its absolute value into the shadow of the same element when there is one */
+static inline void SUF(sink_add)(const SUF(sink_t) *k, REAL *dst, REAL v, int atomic) {
+    SUF(acc)(dst, v, atomic);
+    if (k->mag_base) {
+        double *m = k->mag_base + (dst - k->base);
+        const double a = fabs((double)v);
+        if (atomic) {
+#pragma omp atomic
+            *m += a;
+        } else {
+            *m += a;
+        }
+    }
+}
 
 static inline REAL *SUF(sink_row)(const SUF(sink_t) *k, uint32_t cell, int A, REAL **pg, REAL **pe) {
 #if RFO_HALF_FACES
@@ -453,7 +473,7 @@ static void SUF(backward_ray)(const SUF(foam_t) *fm, const REAL *ray6, uint32_t 
             if (want_err) {
                 REAL *xpg, *xpe;
                 (void)SUF(sink_row)(sink, cur, A, &xpg, &xpe);
-                SUF(acc)(xpe, w * err, atomic);
+                SUF(sink_add)(sink, xpe, w * err, atomic);
             }
 
             REAL dL_drgb[3] = {g[0] * w, g[1] * w, g[2] * w};
@@ -500,9 +520,9 @@ static void SUF(backward_ray)(const SUF(foam_t) *fm, const REAL *ray6, uint32_t 
             if (prev != RFO_NONE) {
                 REAL *xpg, *xpe;
                 (void)SUF(sink_row)(sink, prev, A, &xpg, &xpe);
-                SUF(acc)(xpg + 0, prev_g[0], atomic);
-                SUF(acc)(xpg + 1, prev_g[1], atomic);
-                SUF(acc)(xpg + 2, prev_g[2], atomic);
+                SUF(sink_add)(sink, xpg + 0, prev_g[0], atomic);
+                SUF(sink_add)(sink, xpg + 1, prev_g[1], atomic);
+                SUF(sink_add)(sink, xpg + 2, prev_g[2], atomic);
             }
             for (int i = 0; i < 3; ++i) {
                 prevP[i] = P[i];
@@ -518,8 +538,8 @@ static void SUF(backward_ray)(const SUF(foam_t) *fm, const REAL *ray6, uint32_t 
                 if (rgb[i] == (REAL)0) dL_drgb[i] = (REAL)0;
             REAL *xpg, *xpe;
             REAL *row = SUF(sink_row)(sink, cur, A, &xpg, &xpe);
-            for (int i = 0; i < A - 1; ++i) SUF(acc)(row + i, sh[i / 3] * dL_drgb[i % 3], atomic);
-            SUF(acc)(row + (A - 1), dL_ds, atomic);
+            for (int i = 0; i < A - 1; ++i) SUF(sink_add)(sink, row + i, sh[i / 3] * dL_drgb[i % 3], atomic);
+            SUF(sink_add)(sink, row + (A - 1), dL_ds, atomic);
 
             if (!(T > thr)) break;
         }
@@ -533,8 +553,8 @@ static void SUF(backward_ray)(const SUF(foam_t) *fm, const REAL *ray6, uint32_t 
         /* clean variant: flush what the reference drops */
         REAL *apg, *bpg, *xpe;
         (void)SUF(sink_row)(sink, prev, A, &apg, &xpe);
-        for (int i = 0; i < 3; ++i) SUF(acc)(apg + i, prev_g[i], atomic);
+        for (int i = 0; i < 3; ++i) SUF(sink_add)(sink, apg + i, prev_g[i], atomic);
         (void)SUF(sink_row)(sink, last_nxt, A, &bpg, &xpe);
-        for (int i = 0; i < 3; ++i) SUF(acc)(bpg + i, cur_g[i], atomic);
+        for (int i = 0; i < 3; ++i) SUF(sink_add)(sink, bpg + i, cur_g[i], atomic);
     }
 }

@@ -40,7 +40,7 @@ def to_torch_foam(fm, device, attr_dtype=None):
 
 
 def half_backward_case(foam_factory, d, seed, image, quantiles, with_error, n_points=5000, width=80, height=56,
-                       n_rays=4000):
+                       n_rays=4000, return_magnitude=False):
     """One fp16 forward+backward case with the CPU oracle's answers, computed once (num_threads=1) and shared.
 
     Inputs: the foam's attributes, the upstream rgba gradient (normal(0,1)) and ray_error (uniform(0,1)) are fp16;
@@ -62,11 +62,12 @@ def half_backward_case(foam_factory, d, seed, image, quantiles, with_error, n_po
         dg = rng.normal(size=batch + (2,)).astype(np.float32)
     g = rng.normal(0, 1, size=batch + (4,)).astype(np.float16)
     err = rng.uniform(0, 1, size=batch).astype(np.float16) if with_error else None
-    return half_reference(d, fm, rays, starts, q, dg, g, err)
+    return half_reference(d, fm, rays, starts, q, dg, g, err, return_magnitude=return_magnitude)
 
 
-def half_reference(d, fm, rays, starts, q, dg, g, err):
-    """The oracle's answers for one fp16 case (see half_backward_case), one thread."""
+def half_reference(d, fm, rays, starts, q, dg, g, err, return_magnitude=False):
+    """The oracle's answers for one fp16 case (see half_backward_case), one thread.  return_magnitude: `bwd` and `bwd32`
+    carry the magnitude of every gradient element as well (oracle.trace_backward)."""
     from oracle import oracle as O
 
     assert fm["attributes"].dtype == np.float16 and g.dtype == np.float16 and (err is None or err.dtype == np.float16)
@@ -77,6 +78,8 @@ def half_reference(d, fm, rays, starts, q, dg, g, err):
     fwd = O.trace_forward(*a16, rays, starts, depth_quantiles=q, return_contribution=True, num_threads=1)
     fwd32 = O.trace_forward(*a32, rays, starts, depth_quantiles=q, return_contribution=True, num_threads=1)
     kw = dict(depth_quantiles=q, depth_indices=fwd.get("depth_indices"), depth_grad_in=dg, num_threads=1)
+    if return_magnitude:
+        kw["return_magnitude"] = True
     bwd = O.trace_backward(*a16, rays, starts, fwd["rgba"], g, ray_error=err, **kw)
     bwd32 = O.trace_backward(*a32, rays, starts, wide(fwd["rgba"]), wide(g), ray_error=wide(err), **kw)
     return {"d": d, "fm": fm, "rays": rays, "starts": starts, "q": q, "dg": dg, "g": g, "err": err,
@@ -122,3 +125,93 @@ def grad_close(got, ref, rtol=1e-3):
     bound = rtol * np.abs(ref) + rtol * rms
     rel_l2 = np.linalg.norm(got - ref) / max(np.linalg.norm(ref), 1e-30)
     return bool((err <= bound).all()), float(rel_l2), float((err / np.maximum(bound, 1e-30)).max())
+
+
+def grad_close_elements(got, ref, mag, k, extra_rel=0.0, extra_abs=0.0):
+    """Per-element gradient parity, each element on its own scale.
+
+    `mag[i]` is the sum of |addend| over everything the oracle adds into element i (oracle.trace_backward(...,
+    return_magnitude=True)): rounding and the order of the sum can move the element by a few 2^-24 * mag[i] and no
+    more, whatever the rest of the tensor holds.  Requires |got - ref| <= k * 2^-24 * mag + (2^-22 + extra_rel) * |ref|
+    on every element, and got == 0 exactly where mag == 0 (nothing was added there).  `extra_rel` and `extra_abs` are for
+    an output rounded once more on its way out: an fp16 output of an fp32 sum is half an fp16 step from it, 2^-11 relative
+    for a normal half and 2^-25 absolute among the subnormal ones (|x| < 2^-14), where the step no longer shrinks with x;
+    `extra_abs` is added to the bound of the touched elements only.
+
+    Returns (ok, worst_ratio, index_of_worst): worst_ratio is the largest |got - ref| / (2^-24 * mag) over the touched
+    elements (inf if an untouched element is not 0, nan counts as inf), index_of_worst its index as a tuple."""
+    got = np.asarray(got, dtype=np.float64)
+    ref = np.asarray(ref, dtype=np.float64)
+    mag = np.asarray(mag, dtype=np.float64)
+    assert got.shape == ref.shape == mag.shape, (got.shape, ref.shape, mag.shape)
+    touched = mag != 0
+    err = np.abs(got - ref)
+    bound = k * 2.0 ** -24 * mag + (2.0 ** -22 + extra_rel) * np.abs(ref) + np.where(touched, extra_abs, 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(touched, err / (2.0 ** -24 * mag), np.where(got == 0, 0.0, np.inf))
+    ratio = np.where(np.isnan(ratio), np.inf, ratio)
+    ok = bool((err <= bound).all()) and bool((got[~touched] == 0).all())
+    if ratio.size == 0:
+        return ok, 0.0, ()
+    flat = int(np.argmax(ratio))
+    return ok, float(ratio.reshape(-1)[flat]), tuple(int(i) for i in np.unravel_index(flat, ratio.shape))
+
+
+GRAD_TENSORS = ("points_grad", "attr_grad", "point_error")
+
+
+def element_k(k0):
+    """The k of grad_close_elements for a case whose oracle, run with the rays in reverse order, differs from itself by
+    k0 (a worst_ratio): 4 * max(k0, 4).  The 4 inside is the floor for cases whose reordering happens to be quiet; the
+    4 outside is for a kernel addend that differs from the oracle's by a rounding or two of its own (a contracted
+    multiply-add, the divide sequence, partial sums held in double and rounded once), which no reordering shows."""
+    return 4.0 * max(float(k0), 4.0)
+
+
+def oracle_backward_elements(d, fm, rays, starts, g, q=None, dg=None, err=None, fwd=None, **settings):
+    """The oracle's forward and backward (one thread) with the magnitude of every gradient element, and k0: the largest
+    worst_ratio, over the gradient tensors, of the same backward with the rays in reverse order against it.  Inputs of
+    any batch shape; fp16 attributes / g / err select the oracle's fp16 mode.  Returns (fwd, ref, k0, k0_by_tensor)."""
+    from oracle import oracle as O
+
+    args = (d, fm["points"], fm["attributes"], fm["point_adjacency"], fm["point_adjacency_offsets"])
+    if fwd is None:
+        fwd = O.trace_forward(*args, rays, starts, depth_quantiles=q, num_threads=1, **settings)
+    ref = O.trace_backward(*args, rays, starts, fwd["rgba"], g, depth_quantiles=q, depth_indices=fwd.get("depth_indices"),
+                           depth_grad_in=dg, ray_error=err, num_threads=1, return_magnitude=True, **settings)
+    n = int(np.prod(rays.shape[:-1]))
+    rev = lambda x, w: None if x is None else np.ascontiguousarray(np.asarray(x).reshape((n,) + w)[::-1])
+    nq = 0 if q is None else q.shape[-1]
+    back = O.trace_backward(*args, rev(rays, (6,)), rev(np.broadcast_to(starts, rays.shape[:-1]), ()),
+                            rev(fwd["rgba"], (4,)), rev(g, (4,)), depth_quantiles=rev(q, (nq,)),
+                            depth_indices=rev(fwd.get("depth_indices"), (nq,)), depth_grad_in=rev(dg, (nq,)),
+                            ray_error=rev(err, ()), num_threads=1, **settings)
+    k0s = {}
+    for key in GRAD_TENSORS:
+        if key in ref:
+            fin = np.isfinite(ref[key].astype(np.float64)) & np.isfinite(ref[key + "_mag"])
+            pick = lambda x: np.where(fin, x, 0.0)
+            k0s[key] = grad_close_elements(pick(back[key]), pick(ref[key]), pick(ref[key + "_mag"]), 0.0)[1]
+    return fwd, ref, max(k0s.values()), k0s
+
+
+def backward_case(foam_factory, d, seed, image, quantiles, with_error, n_points=5000):
+    """The inputs of tests/test_gpu_parity.py::_backward_case, value for value (same foam, rays and draws from the same
+    generator in the same order), with the oracle's answers from oracle_backward_elements.  Returns a dict."""
+    fm = foam_factory(n_points, d, seed)
+    rng = np.random.default_rng(seed)
+    if image:
+        cam, rays, start = camera_setup(fm, 80, 56)
+        starts = np.full(rays.shape[:-1], start, dtype=np.uint32)
+    else:
+        rays, starts = random_rays(fm, 4000, seed=seed + 1)
+    batch = rays.shape[:-1]
+    q = dg = None
+    if quantiles:
+        q = np.sort(rng.uniform(0.02, 0.98, size=batch + (2,)).astype(np.float32), axis=-1)[..., ::-1].copy()
+        dg = rng.normal(size=batch + (2,)).astype(np.float32)
+    g = rng.normal(size=batch + (4,)).astype(np.float32)
+    err = rng.uniform(0, 1, size=batch).astype(np.float32) if with_error else None
+    fwd, ref, k0, k0s = oracle_backward_elements(d, fm, rays, starts, g, q, dg, err)
+    return {"d": d, "fm": fm, "rays": rays, "starts": starts, "q": q, "dg": dg, "g": g, "err": err, "fwd": fwd,
+            "ref": ref, "k0": k0, "k0_by_tensor": k0s, "settings": {}}

@@ -584,3 +584,125 @@ def test_half_step_rule():
     many[1::6] = np.nextafter(np.float16(1.0), np.float16(2.0))  # 100 of 500 non-zero
     assert not H.half_step_check(many, ref)[0]
     assert H.half_step_check(many, ref, max_share=0.25)[0]
+
+
+# ---- the magnitude of every gradient element (trace_backward(..., return_magnitude=True)) ------------------------------
+
+_MAG_CASES = {}
+
+
+def _magnitude_case(foam_factory, half):
+    """A 200-ray flat batch (quantiles, ray_error) on a 3000-point foam, d = 2; fp16 attributes / gradients if `half`."""
+    if half not in _MAG_CASES:
+        d = 2
+        fm = dict(foam_factory(3000, d, 57))
+        rays, starts = H.random_rays(fm, 200, seed=58)
+        rng = np.random.default_rng(59)
+        adt = np.float16 if half else np.float32
+        fm["attributes"] = fm["attributes"].astype(adt)
+        q = np.sort(rng.uniform(0.02, 0.98, size=(200, 2)).astype(np.float32), axis=-1)[..., ::-1].copy()
+        dg = rng.normal(size=(200, 2)).astype(np.float32)
+        g = rng.normal(size=(200, 4)).astype(adt)
+        err = rng.uniform(0, 1, size=200).astype(adt)
+        args = (d, fm["points"], fm["attributes"], fm["point_adjacency"], fm["point_adjacency_offsets"])
+        fwd = O.trace_forward(*args, rays, starts, depth_quantiles=q, num_threads=1)
+        kw = dict(depth_quantiles=q, depth_indices=fwd["depth_indices"], depth_grad_in=dg)
+        _MAG_CASES[half] = (args, rays, starts, fwd, g, err, kw)
+    return _MAG_CASES[half]
+
+
+def _bits(x):
+    x = np.ascontiguousarray(x)
+    return x.view({2: np.uint16, 4: np.uint32, 8: np.uint64}[x.dtype.itemsize])
+
+
+@pytest.mark.parametrize("threads", [1, 4])
+@pytest.mark.parametrize("half", [False, True])
+def test_magnitude_leaves_the_gradients_bit_for_bit(foam_factory, half, threads):
+    """The switch adds outputs and changes none: one thread bit for bit (several threads sum in an order that varies
+    from run to run with or without it, so there the magnitudes are compared with the one-thread ones instead)."""
+    args, rays, starts, fwd, g, err, kw = _magnitude_case(foam_factory, half)
+    plain = O.trace_backward(*args, rays, starts, fwd["rgba"], g, ray_error=err, num_threads=1, **kw)
+    mag = O.trace_backward(*args, rays, starts, fwd["rgba"], g, ray_error=err, num_threads=threads,
+                           return_magnitude=True, **kw)
+    assert sorted(mag) == sorted(list(plain) + [k + "_mag" for k in plain])
+    for key in plain:
+        m = mag[key + "_mag"]
+        assert m.dtype == np.float64 and m.shape == plain[key].shape
+        assert mag[key].dtype == plain[key].dtype
+        if threads == 1:
+            np.testing.assert_array_equal(_bits(mag[key]), _bits(plain[key]), err_msg=key)
+        else:
+            one = O.trace_backward(*args, rays, starts, fwd["rgba"], g, ray_error=err, num_threads=1,
+                                   return_magnitude=True, **kw)[key + "_mag"]
+            np.testing.assert_array_equal(m == 0, one == 0, err_msg=key)
+            np.testing.assert_allclose(m, one, rtol=1e-12, atol=0, err_msg=key)     # double sums, another order
+            ok, worst, where = H.grad_close_elements(mag[key].astype(np.float32), plain[key].astype(np.float32), one, 16,
+                                                     extra_rel=2.0 ** -10 if half and key != "points_grad" else 0.0)
+            assert ok, (key, worst, where)
+
+
+@pytest.mark.parametrize("half", [False, True])
+def test_magnitude_bounds_the_gradient_and_is_zero_where_nothing_was_added(foam_factory, half):
+    args, rays, starts, fwd, g, err, kw = _magnitude_case(foam_factory, half)
+    out = O.trace_backward(*args, rays, starts, fwd["rgba"], g, ray_error=err, num_threads=1, return_magnitude=True, **kw)
+    # the cells any ray adds to: those its walk composites (the exit neighbours included, for the point gradient)
+    for key in ("points_grad", "attr_grad", "point_error"):
+        grad, m = out[key].astype(np.float64), out[key + "_mag"]
+        assert np.isfinite(m).all() and (m >= 0).all()
+        # fp32 sums of fp32 addends: |sum| <= sum|addend| up to the rounding of the partial sums (1e-6 covers a few of
+        # 2^-24 each), and for an fp16 output its one rounding: half a step, 2^-11 relative or 2^-25 among the subnormals
+        rounded = half and key != "points_grad"
+        assert (np.abs(grad) <= m * (1.0 + 1e-6 + (2.0 ** -11 if rounded else 0.0)) + (2.0 ** -25 if rounded else 0.0)).all(), key
+        assert ((m == 0) <= (grad == 0)).all(), key
+        assert 0 < (m != 0).sum() < m.size, key
+    # a cell no ray composites holds exact zeros in every shadow; one that a ray composites with a lit segment holds a
+    # density magnitude
+    cells, t1, n = O.trace_paths(*args[:2], args[2].astype(np.float32), *args[3:], rays, starts, cap=1024)
+    visited = np.zeros(args[1].shape[0], dtype=bool)
+    visited[cells[cells != O.NONE]] = True
+    for key in ("points_grad", "attr_grad", "point_error"):
+        assert (out[key + "_mag"][~visited] == 0).all(), key
+    assert (out["attr_grad_mag"][:, -1] != 0).sum() > 100
+
+
+def test_magnitude_does_not_depend_on_the_sign_of_the_upstream_gradient(foam_factory):
+    """Every addend is linear in (rgba_grad, depth_grad) -- and in ray_error for point_error: negating them negates every
+    addend exactly, so the magnitudes are the same bit for bit and the gradients are the negatives bit for bit."""
+    args, rays, starts, fwd, g, err, kw = _magnitude_case(foam_factory, False)
+    pos = O.trace_backward(*args, rays, starts, fwd["rgba"], g, ray_error=err, num_threads=1, return_magnitude=True, **kw)
+    kwn = dict(kw, depth_grad_in=-kw["depth_grad_in"])
+    neg = O.trace_backward(*args, rays, starts, fwd["rgba"], -g, ray_error=-err, num_threads=1, return_magnitude=True,
+                           **kwn)
+    for key in ("points_grad", "attr_grad", "point_error"):
+        np.testing.assert_array_equal(_bits(pos[key + "_mag"]), _bits(neg[key + "_mag"]), err_msg=key)
+        np.testing.assert_array_equal(pos[key], -neg[key], err_msg=key)
+
+
+def test_magnitude_of_a_batch_against_its_rays_one_by_one(foam_factory):
+    """mag >= sum over the rays of |that ray's own row| (1 - 1e-6): a ray's row is already a sum of its addends, so the
+    sum of the rows' absolute values can only be smaller.  And for one ray alone, mag == |grad| on every element the ray
+    adds to once: attr_grad and point_error everywhere (a ray never composites a cell twice: convex cells), points_grad
+    where the one-ray magnitude says so."""
+    args, rays, starts, fwd, g, err, kw = _magnitude_case(foam_factory, False)
+    whole = O.trace_backward(*args, rays, starts, fwd["rgba"], g, ray_error=err, num_threads=1, return_magnitude=True, **kw)
+    rows = {k: np.zeros_like(whole[k + "_mag"]) for k in ("points_grad", "attr_grad", "point_error")}
+    once = 0
+    for r in range(rays.shape[0]):
+        s = slice(r, r + 1)
+        kr = {k: v[s] for k, v in kw.items()}
+        one = O.trace_backward(*args, rays[s], starts[s], fwd["rgba"][s], g[s], ray_error=err[s], num_threads=1,
+                               return_magnitude=True, **kr)
+        for k in rows:
+            rows[k] += np.abs(one[k].astype(np.float64))
+        for k in ("attr_grad", "point_error"):
+            np.testing.assert_array_equal(one[k + "_mag"], np.abs(one[k].astype(np.float64)), err_msg="%s ray %d" % (k, r))
+        # a point takes one add per segment next to it (as the cell before the segment's own): exact where the addend
+        # written is the only one
+        pg, pm = np.abs(one["points_grad"].astype(np.float64)), one["points_grad_mag"]
+        assert (pm >= pg).all()
+        once += int((pm == pg).sum() - (pm == 0).sum())
+    assert once > 200       # the equality above is not vacuous
+    for k in rows:
+        assert (whole[k + "_mag"] >= rows[k] * (1.0 - 1e-6)).all(), k
+        assert ((whole[k + "_mag"] == 0) == (rows[k] == 0)).all() or k == "points_grad", k
