@@ -36,7 +36,8 @@ EXTRA_HEADERS = [os.path.join(_CSRC, n) for n in ("rf_clip.hpp", "rf_clip_grad.h
                                                       "rf_clip_box_grad.hpp", "rf_clip_box_moments.hpp",
                                                       "rf_clip_box_moments_grad.hpp",
                                                       "rf_clip_box_area_grad.hpp", "rf_cell_wave.hpp",
-                                                      "rf_iso.hpp", "rf_tets.hpp", "rf_locate.hpp")] + [
+                                                      "rf_cell_sweep.hpp", "rf_iso.hpp", "rf_tets.hpp",
+                                                      "rf_locate.hpp")] + [
     os.path.join(os.path.dirname(_HERE), "include", n) for n in ("radfoam_hip_geometry.h", "radfoam_hip_segments.h",
                                                                "radfoam_hip_composite.h",
                                                                "radfoam_hip_geometry_grad.h",

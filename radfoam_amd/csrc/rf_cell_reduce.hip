@@ -34,19 +34,11 @@
 
 #include "../../include/radfoam_hip_cell_reduce.h"
 #include "rf_host.hpp"
-#include "rf_ray_sweep.hpp"
-
-#ifndef RF_CELL_REDUCE_CHUNK
-#define RF_CELL_REDUCE_CHUNK 1024
-#endif
+#include "rf_cell_sweep.hpp"
 
 namespace rf {
 
-constexpr int kCellBlock = 256;
-constexpr int kCellWaves = kCellBlock / 64;
-constexpr int kCellChunk = RF_CELL_REDUCE_CHUNK;           // sorted positions per wave: 256 .. 2048 timed, DESIGN 4.15
 constexpr int kCellGroup = 8;                              // channels per sweep: 8 timed against 4, DESIGN 4.15
-static_assert(kCellChunk >= 64 && kCellChunk % 64 == 0, "a wave sweeps its chunk in whole steps of 64 positions");
 
 struct CellReduceParams {
     int64_t num_cells, total, num_chunks;
@@ -57,13 +49,6 @@ struct CellReduceParams {
     float *out;                  // [N][C]
     double *partial;             // [num_chunks][2][C]
 };
-
-// the cell of position k: -1 for a position outside the list or a cell outside 0 .. N-1
-__device__ __forceinline__ int64_t cell_at(const CellReduceParams &p, int64_t k) {
-    if (k < 0 || k >= p.total) return -1;
-    const int64_t c = p.sorted_cells[k];
-    return c < 0 || c >= p.num_cells ? -1 : c;
-}
 
 template <int NCH>
 __global__ __launch_bounds__(kCellBlock) void reduce_entries_kernel(CellReduceParams p) {
@@ -130,11 +115,6 @@ __global__ __launch_bounds__(kCellBlock) void reduce_entries_kernel(CellReducePa
     }
 }
 
-// chunk j holds a partial[j][0] of `cell`: the list came in from the chunk before
-__device__ __forceinline__ bool came_in(const CellReduceParams &p, int64_t j, int64_t cell) {
-    return j < p.num_chunks && cell_at(p, j * kCellChunk) == cell && cell_at(p, j * kCellChunk - 1) == cell;
-}
-
 __global__ __launch_bounds__(kCellBlock) void reduce_entries_boundaries_kernel(CellReduceParams p) {
     const int lane = (int)(threadIdx.x & 63u);
     const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -190,12 +170,10 @@ using namespace rf;
 
 namespace {
 
-int64_t cell_chunks(int64_t num_entries) { return (num_entries + kCellChunk - 1) / kCellChunk; }
-
 template <int NCH>
 void cell_launch(const CellReduceParams &p, hipStream_t stream) {
-    const int64_t blocks = (p.num_chunks + kCellWaves - 1) / kCellWaves;
-    hipLaunchKernelGGL(reduce_entries_kernel<NCH>, dim3((uint32_t)blocks), dim3(kCellBlock), 0, stream, p);
+    hipLaunchKernelGGL(reduce_entries_kernel<NCH>, dim3((uint32_t)cell_sweep_blocks(p.num_chunks)), dim3(kCellBlock),
+                       0, stream, p);
 }
 
 }  // namespace
@@ -205,8 +183,7 @@ extern "C" {
 uint32_t rf_reduce_entries_chunk(void) { return (uint32_t)kCellChunk; }
 
 size_t rf_reduce_entries_workspace_bytes(int64_t num_entries, uint32_t num_channels) {
-    if (num_entries <= 0) return 0;
-    return (size_t)cell_chunks(num_entries) * 2 * (size_t)num_channels * sizeof(double);
+    return cell_workspace_bytes(num_entries, num_channels);
 }
 
 int rf_reduce_entries(int64_t num_cells, int64_t num_entries, const int64_t *sorted_cells, const int64_t *entries,
@@ -224,10 +201,8 @@ int rf_reduce_entries(int64_t num_cells, int64_t num_entries, const int64_t *sor
         return check_launch(what);
     if (num_entries == 0) return RF_OK;
     if (!sorted_cells || !entries || !values) return fail(RF_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
-    if (!workspace || workspace_bytes < rf_reduce_entries_workspace_bytes(num_entries, num_channels))
-        return fail(RF_ERR_WORKSPACE, "%s: workspace missing or too small", what);
-    if ((reinterpret_cast<uintptr_t>(workspace) & 7u) != 0)
-        return fail(RF_ERR_WORKSPACE, "%s: the workspace must be 8-byte aligned", what);
+    int rc = cell_check(what, num_entries, num_channels, workspace, workspace_bytes);
+    if (rc != RF_OK) return rc;
     CellReduceParams p{};
     p.num_cells = num_cells;
     p.total = num_entries;
@@ -238,8 +213,6 @@ int rf_reduce_entries(int64_t num_cells, int64_t num_entries, const int64_t *sor
     p.values = values;
     p.out = out;
     p.partial = static_cast<double *>(workspace);
-    if ((p.num_chunks + kCellWaves - 1) / kCellWaves >= ((int64_t)1 << 31))
-        return fail(RF_ERR_INVALID_ARGUMENT, "%s: too many entries for one launch", what);
     for (uint32_t first = 0; first < num_channels; first += kCellGroup) {
         p.first_channel = first;
         switch (num_channels - first < (uint32_t)kCellGroup ? num_channels - first : (uint32_t)kCellGroup) {
@@ -252,16 +225,10 @@ int rf_reduce_entries(int64_t num_cells, int64_t num_entries, const int64_t *sor
             case 7: cell_launch<7>(p, s); break;
             default: cell_launch<8>(p, s); break;
         }
-        const int rc = check_launch(what);
+        rc = check_launch(what);
         if (rc != RF_OK) return rc;
     }
-    if (p.num_chunks > 1) {
-        const int64_t waves = (p.num_chunks - 1 + 63) / 64;
-        hipLaunchKernelGGL(reduce_entries_boundaries_kernel, dim3((uint32_t)((waves + kCellWaves - 1) / kCellWaves)),
-                           dim3(kCellBlock), 0, s, p);
-        return check_launch(what);
-    }
-    return RF_OK;
+    return cell_launch_boundaries(what, reduce_entries_boundaries_kernel, p, s);
 }
 
 }  // extern "C"

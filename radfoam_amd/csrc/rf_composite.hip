@@ -42,27 +42,8 @@ using CompSweep = RaySweep<kCompRays, kCompWaves>;
 using CompWave = CompSweep::Wave;
 using CompStep = CompSweep::Step;
 
-// ---- what an entry contributes: zeros where the lane is not valid ----
-struct CompEntry {
-    double dt, sigma, x;
-    bool infinite;     // t_exit is infinite: every gradient of the entry is an exact zero
-    bool moves;        // t_exit is finite and >= t_enter: the times get a gradient (torch's clamp_min convention)
-};
-
-__device__ __forceinline__ CompEntry comp_entry(const CompStep &s, const float *t_enter, const float *t_exit,
-                                                const float *sigma) {
-    CompEntry e{0.0, 0.0, 0.0, false, false};
-    if (s.valid) {
-        const float t0 = t_enter[s.k], t1 = t_exit[s.k];
-        const double d = (double)t1 - (double)t0;
-        e.infinite = __builtin_isinf(t1);
-        e.moves = !e.infinite && t1 >= t0;
-        e.dt = e.infinite ? 0.0 : (d < 0.0 ? 0.0 : d);
-        e.sigma = (double)sigma[s.k];
-        e.x = e.sigma * e.dt;
-    }
-    return e;
-}
+// The running sums, T and w in the backward, and the ray's total of lane i are spelled out here and, in step with
+// this text, in rf_entry_weights.hip and rf_distortion.hip: as calls of shared helpers they change the kernels' code.
 
 struct CompForwardParams {
     uint32_t num_rays, num_channels;
@@ -97,7 +78,7 @@ __global__ __launch_bounds__(kCompBlock) void composite_forward_kernel(CompForwa
     for (int c = 0; c < NCH; ++c) carry[c] = 0.0;
     for (int64_t base = w.first_base(); base < w.hi; base += 64) {
         const CompStep s = CompSweep::step(w, base);
-        const CompEntry e = comp_entry(s, p.t_enter, p.t_exit, p.sigma);
+        const SweepEntry e = sweep_entry(s, p.t_enter, p.t_exit, p.sigma);
         double v[NCH];
 #pragma unroll
         for (int c = 0; c < NCH; ++c) v[c] = 0.0;
@@ -110,7 +91,7 @@ __global__ __launch_bounds__(kCompBlock) void composite_forward_kernel(CompForwa
         double sx[1] = {e.x};
         CompSweep::scan(sx, w.lane, s.begin);
         const double sum_x = s.cont ? sx[0] + carry_x : sx[0];          // the ray's x up to and including this entry
-        const double weight = ::exp(-(sum_x - e.x)) * -::expm1(-e.x);
+        const double weight = sweep_weight(sum_x, e.x).weight;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) v[c] = weight * v[c];
         CompSweep::scan(v, w.lane, s.begin);
@@ -154,7 +135,7 @@ __global__ __launch_bounds__(kCompBlock) void composite_backward_kernel(CompBack
         double carry_x = 0.0, carry_wq = 0.0;
         for (int64_t base = w.first_base(); base < w.hi; base += 64) {
             const CompStep s = CompSweep::step(w, base);
-            const CompEntry e = comp_entry(s, p.t_enter, p.t_exit, p.sigma);
+            const SweepEntry e = sweep_entry(s, p.t_enter, p.t_exit, p.sigma);
             double q = 0.0;
             if (s.valid) {
                 const float *g = p.grad_out + (size_t)(w.r0 + s.ray) * pitch;
@@ -186,7 +167,7 @@ __global__ __launch_bounds__(kCompBlock) void composite_backward_kernel(CompBack
     double carry_x = 0.0, carry_wq = 0.0;
     for (int64_t base = w.first_base(); base < w.hi; base += 64) {
         const CompStep s = CompSweep::step(w, base);
-        const CompEntry e = comp_entry(s, p.t_enter, p.t_exit, p.sigma);
+        const SweepEntry e = sweep_entry(s, p.t_enter, p.t_exit, p.sigma);
         double sx[1] = {e.x};
         CompSweep::scan(sx, w.lane, s.begin);
         const double sum_x = s.cont ? sx[0] + carry_x : sx[0];
@@ -218,11 +199,10 @@ __global__ __launch_bounds__(kCompBlock) void composite_backward_kernel(CompBack
             const double g_alpha = (double)p.grad_out[(size_t)(w.r0 + s.ray) * pitch + C];
             // T_e exp(-x_e) q_e - (the ray's later w q) + G[r][C] exp(-sum x); exp(-x_e) = 1 - alpha_e
             const double dx = __builtin_fma(g_alpha, keep, __builtin_fma(through * (1.0 - alpha), q, -(total_wq - sum_wq)));
-            const double g_sigma = e.infinite ? 0.0 : dx * e.dt;
-            const double g_exit = e.moves ? dx * e.sigma : 0.0;
-            if (p.grad_sigma) p.grad_sigma[s.k] = (float)g_sigma;
-            if (p.grad_t_exit) p.grad_t_exit[s.k] = (float)g_exit;
-            if (p.grad_t_enter) p.grad_t_enter[s.k] = (float)(0.0 - g_exit);
+            const SweepGrad g = sweep_grad(e, dx);
+            if (p.grad_sigma) p.grad_sigma[s.k] = (float)g.sigma;
+            if (p.grad_t_exit) p.grad_t_exit[s.k] = (float)g.exit;
+            if (p.grad_t_enter) p.grad_t_enter[s.k] = (float)(0.0 - g.exit);
         }
     }
 }

@@ -41,27 +41,27 @@ using DistSweep = RaySweep<kDistRays, kDistWaves>;
 using DistWave = DistSweep::Wave;
 using DistStep = DistSweep::Step;
 
-// ---- what an entry brings: zeros where the lane is not valid ----
+// ---- what an entry brings: zeros where the lane is not valid.  dt, sigma, x, infinite and moves are SweepEntry's,
+// taken over from it in the one branch that also reads the interval; the members stand in this order because another
+// one, a struct derived from SweepEntry too, changes the kernels' code ----
 struct DistEntry {
     double dt, sigma, x;
     double m, d;       // midpoint and width in the measure of the distortion; 0, selected, where t_exit is infinite
-    bool infinite;     // t_exit is infinite: every gradient of the entry is an exact zero
-    bool moves;        // t_exit is finite and >= t_enter: the times get a gradient through w (torch's clamp_min)
-    bool widens;       // not infinite and b >= a: d passes its gradient on (the same convention)
+    bool infinite, moves;
+    bool widens;       // not infinite and b >= a: d passes its gradient on (the convention of moves)
 };
 
 __device__ __forceinline__ DistEntry dist_entry(const DistStep &s, const float *t_enter, const float *t_exit,
                                                 const float *sigma, const float *s_enter, const float *s_exit) {
     DistEntry e{0.0, 0.0, 0.0, 0.0, 0.0, false, false, false};
     if (s.valid) {
-        const float t0 = t_enter[s.k], t1 = t_exit[s.k];
-        const double gap = (double)t1 - (double)t0;
-        e.infinite = __builtin_isinf(t1);
-        e.moves = !e.infinite && t1 >= t0;
-        e.dt = e.infinite ? 0.0 : (gap < 0.0 ? 0.0 : gap);
-        e.sigma = (double)sigma[s.k];
-        e.x = e.sigma * e.dt;
-        const float a = s_enter ? s_enter[s.k] : t0, b = s_exit ? s_exit[s.k] : t1;
+        const SweepEntry in = sweep_entry_at(s.k, t_enter, t_exit, sigma);
+        e.infinite = in.infinite;
+        e.moves = in.moves;
+        e.dt = in.dt;
+        e.sigma = in.sigma;
+        e.x = in.x;
+        const float a = s_enter ? s_enter[s.k] : in.t0, b = s_exit ? s_exit[s.k] : in.t1;
         const double width = (double)b - (double)a;
         e.widens = !e.infinite && b >= a;
         e.m = e.infinite ? 0.0 : ((double)a + (double)b) * 0.5;
@@ -86,12 +86,11 @@ struct DistWeights {
 __device__ __forceinline__ DistWeights dist_weights(const DistWave &wv, const DistStep &s, const DistEntry &e,
                                                     DistCarry &carry) {
     DistWeights o;
-    double sx[1] = {e.x};
-    DistSweep::scan(sx, wv.lane, s.begin);
-    const double sum_x = s.cont ? sx[0] + carry.x : sx[0];
-    o.through = ::exp(-(sum_x - e.x));
-    o.alpha = -::expm1(-e.x);
-    o.w = o.through * o.alpha;
+    const double sum_x = DistSweep::running(wv, s, e.x, carry.x);
+    const SweepWeight t = sweep_weight(sum_x, e.x);
+    o.through = t.through;
+    o.alpha = t.alpha;
+    o.w = t.weight;
     const double wm = o.w * e.m;
     double v[2] = {o.w, wm};
     DistSweep::scan(v, wv.lane, s.begin);
@@ -131,14 +130,14 @@ __device__ __forceinline__ void dist_totals(const DistWave &w, const DistParams 
         const DistEntry e = dist_entry(s, p.t_enter, p.t_exit, p.sigma, p.s_enter, p.s_exit);
         const DistWeights q = dist_weights(w, s, e, carry);
         // the entry's share: 2 w (m W< - M<) + w^2 d / 3
-        double share[1] = {2.0 * q.w * (e.m * q.before_w - q.before_wm) + q.w * q.w * e.d / 3.0};
-        DistSweep::scan(share, w.lane, s.begin);
-        const double sum_out = s.cont ? share[0] + carry_out : share[0];
+        const double share = 2.0 * q.w * (e.m * q.before_w - q.before_wm) + q.w * q.w * e.d / 3.0;
+        const double sum_out = DistSweep::running(w, s, share, carry_out);
         carry_out = DistSweep::carry(s, sum_out);
 
+        // the ray's totals to lane i: spelled out as in rf_composite.hip's first sweep, keep in step
         const bool here = mine && my_last >= base && my_last < base + 64;
         const int src = here ? (int)(my_last - base) : w.lane;
-        const double end_w = DistSweep::from_lane(q.upto_w, src), end_wm = DistSweep::from_lane(q.upto_wm, src);
+        const double end_w =DistSweep::from_lane(q.upto_w, src), end_wm = DistSweep::from_lane(q.upto_wm, src);
         const double end_out = DistSweep::from_lane(sum_out, src);
         if (here) {
             ray_w = end_w;
@@ -199,11 +198,10 @@ __global__ __launch_bounds__(kDistBlock) void ray_distortion_backward_kernel(Dis
         if (s.valid) {
             // T_i exp(-x_i) g_i - (the ray's later w g); exp(-x_i) = 1 - alpha_i
             const double dx = g_ray * (q.through * (1.0 - q.alpha) * g_w - (2.0 * total_out - sum_wg));
-            const double g_sigma = e.infinite ? 0.0 : dx * e.dt;
-            const double g_exit = e.moves ? dx * e.sigma : 0.0;
-            if (p.grad_sigma) p.grad_sigma[s.k] = (float)g_sigma;
-            if (p.grad_t_exit) p.grad_t_exit[s.k] = (float)(own_measure ? g_exit : g_exit + g_b);
-            if (p.grad_t_enter) p.grad_t_enter[s.k] = (float)(own_measure ? 0.0 - g_exit : g_a - g_exit);
+            const SweepGrad g = sweep_grad(e, dx);
+            if (p.grad_sigma) p.grad_sigma[s.k] = (float)g.sigma;
+            if (p.grad_t_exit) p.grad_t_exit[s.k] = (float)(own_measure ? g.exit : g.exit + g_b);
+            if (p.grad_t_enter) p.grad_t_enter[s.k] = (float)(own_measure ? 0.0 - g.exit : g_a - g.exit);
         }
     }
 }

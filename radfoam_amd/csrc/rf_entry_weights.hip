@@ -36,27 +36,7 @@ using WeightSweep = RaySweep<kWeightRays, kWeightWaves>;
 using WeightWave = WeightSweep::Wave;
 using WeightStep = WeightSweep::Step;
 
-// ---- what an entry contributes: zeros where the lane is not valid ----
-struct WeightEntry {
-    double dt, sigma, x;
-    bool infinite;     // t_exit is infinite: the weight and every gradient of the entry are exact zeros
-    bool moves;        // t_exit is finite and >= t_enter: the times get a gradient (torch's clamp_min convention)
-};
-
-__device__ __forceinline__ WeightEntry weight_entry(const WeightStep &s, const float *t_enter, const float *t_exit,
-                                                    const float *sigma) {
-    WeightEntry e{0.0, 0.0, 0.0, false, false};
-    if (s.valid) {
-        const float t0 = t_enter[s.k], t1 = t_exit[s.k];
-        const double d = (double)t1 - (double)t0;
-        e.infinite = __builtin_isinf(t1);
-        e.moves = !e.infinite && t1 >= t0;
-        e.dt = e.infinite ? 0.0 : (d < 0.0 ? 0.0 : d);
-        e.sigma = (double)sigma[s.k];
-        e.x = e.sigma * e.dt;
-    }
-    return e;
-}
+// The running sums, T and w, and the ray's total of lane i below are spelled out as in rf_composite.hip: keep in step.
 
 struct WeightForwardParams {
     uint32_t num_rays;
@@ -74,7 +54,7 @@ __global__ __launch_bounds__(kWeightBlock) void entry_weights_forward_kernel(Wei
     double carry_x = 0.0;
     for (int64_t base = w.first_base(); base < w.hi; base += 64) {
         const WeightStep s = WeightSweep::step(w, base);
-        const WeightEntry e = weight_entry(s, p.t_enter, p.t_exit, p.sigma);
+        const SweepEntry e = sweep_entry(s, p.t_enter, p.t_exit, p.sigma);
         double sx[1] = {e.x};
         WeightSweep::scan(sx, w.lane, s.begin);
         const double sum_x = s.cont ? sx[0] + carry_x : sx[0];          // the ray's x up to and including this entry
@@ -125,7 +105,7 @@ __global__ __launch_bounds__(kWeightBlock) void entry_weights_backward_kernel(We
         double carry_x = 0.0, carry_u = 0.0;
         for (int64_t base = w.first_base(); base < w.hi; base += 64) {
             const WeightStep s = WeightSweep::step(w, base);
-            const WeightEntry e = weight_entry(s, p.t_enter, p.t_exit, p.sigma);
+            const SweepEntry e = sweep_entry(s, p.t_enter, p.t_exit, p.sigma);
             double sx[1] = {e.x};
             WeightSweep::scan(sx, w.lane, s.begin);
             const double sum_x = s.cont ? sx[0] + carry_x : sx[0];
@@ -149,7 +129,7 @@ __global__ __launch_bounds__(kWeightBlock) void entry_weights_backward_kernel(We
     double carry_x = 0.0, carry_u = 0.0;
     for (int64_t base = w.first_base(); base < w.hi; base += 64) {
         const WeightStep s = WeightSweep::step(w, base);
-        const WeightEntry e = weight_entry(s, p.t_enter, p.t_exit, p.sigma);
+        const SweepEntry e = sweep_entry(s, p.t_enter, p.t_exit, p.sigma);
         double sx[1] = {e.x};
         WeightSweep::scan(sx, w.lane, s.begin);
         const double sum_x = s.cont ? sx[0] + carry_x : sx[0];
@@ -167,11 +147,10 @@ __global__ __launch_bounds__(kWeightBlock) void entry_weights_backward_kernel(We
         if (s.valid) {
             // g_w[e] T_e exp(-x_e) - (the ray's later u); exp(-x_e) = 1 - alpha_e
             const double dx = __builtin_fma(through * (1.0 - alpha), g_w, -(total_u - sum_u));
-            const double g_sigma = e.infinite ? 0.0 : dx * e.dt;
-            const double g_exit = e.moves ? dx * e.sigma : 0.0;
-            if (p.grad_sigma) p.grad_sigma[s.k] = (float)g_sigma;
-            if (p.grad_t_exit) p.grad_t_exit[s.k] = (float)g_exit;
-            if (p.grad_t_enter) p.grad_t_enter[s.k] = (float)(0.0 - g_exit);
+            const SweepGrad g = sweep_grad(e, dx);
+            if (p.grad_sigma) p.grad_sigma[s.k] = (float)g.sigma;
+            if (p.grad_t_exit) p.grad_t_exit[s.k] = (float)g.exit;
+            if (p.grad_t_enter) p.grad_t_enter[s.k] = (float)(0.0 - g.exit);
         }
     }
 }

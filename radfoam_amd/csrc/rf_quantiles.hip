@@ -46,40 +46,15 @@ using QuantWave = QuantSweep::Wave;
 using QuantStep = QuantSweep::Step;
 static_assert(kQuantMax >= 1 && kQuantMax <= 32, "the carried mask of crossed quantiles is one 32-bit register");
 
-// ---- what an entry brings: zeros where the lane is not valid ----
-struct QuantEntry {
-    double t0, dt, sigma, x;
-    bool infinite;     // t_exit is infinite: every gradient of the entry is an exact zero
-    bool moves;        // t_exit is finite and >= t_enter: the times get a gradient through x (torch's clamp_min)
-};
-
-__device__ __forceinline__ QuantEntry quant_entry(const QuantStep &s, const float *t_enter, const float *t_exit,
-                                                  const float *sigma) {
-    QuantEntry e{0.0, 0.0, 0.0, 0.0, false, false};
-    if (s.valid) {
-        const float t0 = t_enter[s.k], t1 = t_exit[s.k];
-        const double gap = (double)t1 - (double)t0;
-        e.infinite = __builtin_isinf(t1);
-        e.moves = !e.infinite && t1 >= t0;
-        e.t0 = (double)t0;
-        e.dt = e.infinite ? 0.0 : (gap < 0.0 ? 0.0 : gap);
-        e.sigma = (double)sigma[s.k];
-        e.x = e.sigma * e.dt;
-    }
-    return e;
-}
-
 // ---- the sums of a step: upto = I_k, before = X_k as the bits the entry before holds as I ----
 struct QuantSums {
     double upto, before;
 };
 
-__device__ __forceinline__ QuantSums quant_sums(const QuantWave &w, const QuantStep &s, const QuantEntry &e,
+__device__ __forceinline__ QuantSums quant_sums(const QuantWave &w, const QuantStep &s, const SweepEntry &e,
                                                 double &carry_x) {
     QuantSums o;
-    double sx[1] = {e.x};
-    QuantSweep::scan(sx, w.lane, s.begin);
-    o.upto = s.cont ? sx[0] + carry_x : sx[0];
+    o.upto = QuantSweep::running(w, s, e.x, carry_x);
     const double below = QuantSweep::from_lane(o.upto, (w.lane - 1) & 63);
     o.before = w.lane > s.begin ? below : (s.cont ? carry_x : 0.0);
     carry_x = QuantSweep::carry(s, o.upto);
@@ -110,7 +85,7 @@ __global__ __launch_bounds__(kQuantBlock) void ray_quantiles_forward_kernel(Quan
     uint32_t carry_done = 0;                                             // of the ray that runs past the step before
     for (int64_t base = w.first_base(); base < w.hi; base += 64) {
         const QuantStep s = QuantSweep::step(w, base);
-        const QuantEntry e = quant_entry(s, p.t_enter, p.t_exit, p.sigma);
+        const SweepEntry e = sweep_entry(s, p.t_enter, p.t_exit, p.sigma);
         const uint32_t done_before = s.cont ? carry_done : 0u;
         const QuantSums sum = quant_sums(w, s, e, carry_x);
         const uint64_t my_run = (~(uint64_t)0 << s.begin) & below_me;    // the lanes of my run below me
@@ -122,7 +97,7 @@ __global__ __launch_bounds__(kQuantBlock) void ray_quantiles_forward_kernel(Quan
             const uint64_t ballot = __builtin_amdgcn_ballot_w64(above);
             const bool prior = ((done_before >> q) & 1u) != 0 || (ballot & my_run) != 0;
             if (above && !prior) {                                       // the lowest lane of the ray above the level
-                p.depth[row + q] = (float)(e.t0 + (level - sum.before) / e.sigma);
+                p.depth[row + q] = (float)((double)e.t0 + (level - sum.before) / e.sigma);
                 p.entries[row + q] = s.k;
             }
             if (above || prior) done |= 1u << q;
@@ -153,7 +128,7 @@ __global__ __launch_bounds__(kQuantBlock) void ray_quantiles_backward_kernel(Qua
     double carry_x = 0.0;
     for (int64_t base = w.first_base(); base < w.hi; base += 64) {
         const QuantStep s = QuantSweep::step(w, base);
-        const QuantEntry e = quant_entry(s, p.t_enter, p.t_exit, p.sigma);
+        const SweepEntry e = sweep_entry(s, p.t_enter, p.t_exit, p.sigma);
         const QuantSums sum = quant_sums(w, s, e, carry_x);
         if (s.valid) {                                                   // no cross-lane operation in here
             const int64_t row = (w.r0 + s.ray) * num_q;

@@ -1,6 +1,6 @@
 // rf_ray_sweep.hpp -- the wave scheme of the kernels that go over an exported walk ray by ray (rf_composite.hip,
-// rf_distortion.hip, rf_quantiles.hip), and the 64-bit lane exchange and the segmented scan over
-// a wave, which other kernels use without the rays (rf_segments_rays_grad.hip, rf_cell_reduce.hip).
+// rf_distortion.hip, rf_quantiles.hip, rf_entry_weights.hip) with what an entry contributes to
+// them, and the lane exchange and the segmented scan for those without rays (rf_segments_rays_grad.hip, the cell sweeps).
 //
 // ONE WAVE OWNS kRays CONSECUTIVE RAYS and sweeps their contiguous range of entries 64 at a time, one lane per entry,
 // from the 64-aligned entry at or below the range's first: every [S] array is read coalesced.  No ray is shared between
@@ -155,6 +155,75 @@ struct RaySweep : WaveLanes {
     static __device__ __forceinline__ double carry(const Step &s, double sum) {
         return from_lane(s.last && !s.ends ? sum : 0.0, 63);
     }
+
+    // the sum of v over the lane's ray up to and including its entry: the scan over its run in this step, and what the
+    // ray carried in.  For helpers such as quant_sums and dist_weights only: called from a kernel's own body it changes
+    // the kernel's code, so the kernels spell these three lines out, array, scan and cont, as they stand
+    // here.
+    static __device__ __forceinline__ double running(const Wave &w, const Step &s, double v, double carried) {
+        double a[1] = {v};
+        scan(a, w.lane, s.begin);
+        return s.cont ? a[0] + carried : a[0];
+    }
 };
+
+// ---- what an entry of the walk contributes: zeros where the lane is not valid.  THE ONE STATEMENT, for every
+// operator over the walk, of
+//     dt = 0 where t_exit is infinite, else max(t_exit - t_enter, 0),      x = sigma dt ----
+struct SweepEntry {
+    float t0, t1;      // t_enter and t_exit as read
+    double dt, sigma, x;
+    bool infinite;     // t_exit is infinite: every gradient of the entry is an exact zero
+    bool moves;        // t_exit is finite and >= t_enter: the times get a gradient (torch's clamp_min convention)
+};
+
+// entry k, for a lane that may read it
+__device__ __forceinline__ SweepEntry sweep_entry_at(int64_t k, const float *t_enter, const float *t_exit,
+                                                     const float *sigma) {
+    SweepEntry e;
+    e.t0 = t_enter[k];
+    e.t1 = t_exit[k];
+    const double d = (double)e.t1 - (double)e.t0;
+    e.infinite = __builtin_isinf(e.t1);
+    e.moves = !e.infinite && e.t1 >= e.t0;
+    e.dt = e.infinite ? 0.0 : (d < 0.0 ? 0.0 : d);
+    e.sigma = (double)sigma[k];
+    e.x = e.sigma * e.dt;
+    return e;
+}
+
+// the entry of a step's lane
+template <class Step>
+__device__ __forceinline__ SweepEntry sweep_entry(const Step &s, const float *t_enter, const float *t_exit,
+                                                  const float *sigma) {
+    SweepEntry e{};
+    if (s.valid) e = sweep_entry_at(s.k, t_enter, t_exit, sigma);
+    return e;
+}
+
+// T = exp(-(the ray's earlier x)), alpha = 1 - exp(-x) and w = T alpha of an entry, from the ray's x up to and
+// including it
+struct SweepWeight {
+    double through, alpha, weight;
+};
+
+__device__ __forceinline__ SweepWeight sweep_weight(double sum_x, double x) {
+    SweepWeight o;
+    o.through = ::exp(-(sum_x - x));                       // exp(-0) = 1 at a ray's first entry
+    o.alpha = -::expm1(-x);
+    o.weight = o.through * o.alpha;
+    return o;
+}
+
+// dL/dx of an entry handed on to sigma and to t_exit; t_enter gets the negative of the latter.  Entry: SweepEntry, or
+// an entry that states dt, sigma, infinite and moves as SweepEntry does.
+struct SweepGrad {
+    double sigma, exit;
+};
+
+template <class Entry>
+__device__ __forceinline__ SweepGrad sweep_grad(const Entry &e, double dx) {
+    return SweepGrad{e.infinite ? 0.0 : dx * e.dt, e.moves ? dx * e.sigma : 0.0};
+}
 
 }  // namespace rf

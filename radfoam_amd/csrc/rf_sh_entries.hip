@@ -12,12 +12,12 @@
 //
 // BACKWARD TO THE COEFFICIENTS: the sum per cell of rf_cell_reduce.hip with the row formed in registers: at sorted
 // position k with entry e and ray r the row is Y_k'(dhat_r) (rgb[e][c] > 0 ? g[e][c] : 0), each product rounded to fp32
-// (what the reference adds per entry), summed in double over the cell's run, rounded once.  THE POSITION SWEEP BELOW
-// IS A SECOND STATEMENT OF reduce_entries_kernel AND reduce_entries_boundaries_kernel OF rf_cell_reduce.hip, which is
-// left as it was measured: a wave owns kShChunk consecutive positions whatever the list lengths are,
-// lists that cross chunks leave their per-chunk sums in partial[chunk][2][C] and are finished in chunk order by the
-// boundary launch, cells without entries keep the zeros of one clearing fill.  An edit to the scheme there belongs
-// here too.  Channels go in groups of kShGroup whole basis functions, one sweep per group.
+// (what the reference adds per entry), summed in double over the cell's run, rounded once.  The scheme is
+// rf_cell_sweep.hpp's, which also holds what the two users state once: the chunk, the workspace, the checks, the launch
+// sizes, cell_at and came_in.  The bodies of the two kernels below follow reduce_entries_kernel and
+// reduce_entries_boundaries_kernel of rf_cell_reduce.hip line by line, but for where a lane's row and the first channel
+// come from: an edit to either pair belongs in the other (DESIGN 4.16 lists the shared spellings that changed the
+// kernels' code).  Channels go in groups of kShGroup whole basis functions, one sweep per group.
 //
 // BACKWARD TO THE DIRECTIONS: one lane per entry in entry order under rf_ray_sweep.hpp's RaySweep.  Per entry
 // q_e = sum_c m g[e][c] sum_k grad Y_k(dhat) coeffs[cell][3 k + c], in double; the three components are summed per ray
@@ -32,15 +32,11 @@
 
 #include <stdint.h>
 
-#include "../../include/radfoam_hip_cell_reduce.h"
 #include "../../include/radfoam_hip_sh_entries.h"
 #include "rf_host.hpp"
+#include "rf_cell_sweep.hpp"
 #include "rf_math.hpp"
-#include "rf_ray_sweep.hpp"
 
-#ifndef RF_CELL_REDUCE_CHUNK
-#define RF_CELL_REDUCE_CHUNK 1024
-#endif
 #ifndef RF_SH_ENTRIES_GROUP
 #define RF_SH_ENTRIES_GROUP 8
 #endif
@@ -49,10 +45,8 @@ namespace rf {
 
 constexpr int kShBlock = 256;
 constexpr int kShWaves = kShBlock / 64;
-constexpr int kShChunk = RF_CELL_REDUCE_CHUNK;             // sorted positions per wave: rf_cell_reduce.hip's
 constexpr int kShGroup = RF_SH_ENTRIES_GROUP;              // basis functions per sweep: 8 of 1, 2, 4, 8 timed, DESIGN 4.16
 constexpr int kShRays = 8;                                 // rays per wave of the direction gradient
-static_assert(kShChunk >= 64 && kShChunk % 64 == 0, "a wave sweeps its chunk in whole steps of 64 positions");
 static_assert(kShGroup == 1 || kShGroup == 2 || kShGroup == 4 || kShGroup == 8, "3, 6, 12 or 24 channels per sweep");
 using ShSweep = RaySweep<kShRays, kShWaves>;
 
@@ -128,7 +122,7 @@ __global__ __launch_bounds__(kShBlock) void sh_entries_forward_kernel(ShForwardP
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// backward to the coefficients: rf_cell_reduce.hip's position sweep, restated (see the head of this file)
+// backward to the coefficients: rf_cell_sweep.hpp's scheme; the bodies follow rf_cell_reduce.hip's (see the head)
 
 struct ShCoeffParams {
     int64_t num_cells, total, num_chunks;
@@ -142,24 +136,17 @@ struct ShCoeffParams {
     double *partial;             // [num_chunks][2][3 K]
 };
 
-// the cell of position k: -1 for a position outside the list or a cell outside 0 .. N-1
-__device__ __forceinline__ int64_t sh_cell_at(const ShCoeffParams &p, int64_t k) {
-    if (k < 0 || k >= p.total) return -1;
-    const int64_t c = p.sorted_cells[k];
-    return c < 0 || c >= p.num_cells ? -1 : c;
-}
-
 // this launch sums basis functions FIRST .. FIRST + NB - 1: channels 3 FIRST .. 3 (FIRST + NB) - 1
 template <int DEG, int FIRST, int NB>
-__global__ __launch_bounds__(kShBlock) void sh_entries_coeffs_kernel(ShCoeffParams p) {
+__global__ __launch_bounds__(kCellBlock) void sh_entries_coeffs_kernel(ShCoeffParams p) {
     constexpr int NCH = 3 * NB;
     const int lane = (int)(threadIdx.x & 63u);
     const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t chunk = (int64_t)blockIdx.x * kShWaves + wave_in_block;
+    const int64_t chunk = (int64_t)blockIdx.x * kCellWaves + wave_in_block;
     if (chunk >= p.num_chunks) return;
-    const int64_t c0 = chunk * kShChunk;
-    const int64_t c1 = c0 + kShChunk < p.total ? c0 + kShChunk : p.total;
-    const int64_t cell_before = sh_cell_at(p, c0 - 1);                   // wave-uniform
+    const int64_t c0 = chunk * kCellChunk;
+    const int64_t c1 = c0 + kCellChunk < p.total ? c0 + kCellChunk : p.total;
+    const int64_t cell_before = cell_at(p, c0 - 1);                   // wave-uniform
     const uint64_t upto_me = ~(uint64_t)0 >> (63 - lane);
     const size_t C = p.num_channels;
 
@@ -170,8 +157,8 @@ __global__ __launch_bounds__(kShBlock) void sh_entries_coeffs_kernel(ShCoeffPara
     for (int64_t base = c0; base < c1; base += 64) {
         const int64_t k = base + lane;
         const bool in = k < c1;
-        const int64_t cell = in ? sh_cell_at(p, k) : -1;
-        const int64_t next = in ? sh_cell_at(p, k + 1) : -1;
+        const int64_t cell = in ? cell_at(p, k) : -1;
+        const int64_t next = in ? cell_at(p, k + 1) : -1;
         const bool chunk_end = k + 1 == c1;
         const bool same_next = cell >= 0 && next == cell;
         const bool run_end = !same_next || chunk_end;                    // the last lane of its run within the chunk
@@ -225,16 +212,11 @@ __global__ __launch_bounds__(kShBlock) void sh_entries_coeffs_kernel(ShCoeffPara
     }
 }
 
-// chunk j holds a partial[j][0] of `cell`: the list came in from the chunk before
-__device__ __forceinline__ bool sh_came_in(const ShCoeffParams &p, int64_t j, int64_t cell) {
-    return j < p.num_chunks && sh_cell_at(p, j * kShChunk) == cell && sh_cell_at(p, j * kShChunk - 1) == cell;
-}
-
-__global__ __launch_bounds__(kShBlock) void sh_entries_coeffs_boundaries_kernel(ShCoeffParams p) {
+__global__ __launch_bounds__(kCellBlock) void sh_entries_coeffs_boundaries_kernel(ShCoeffParams p) {
     const int lane = (int)(threadIdx.x & 63u);
     const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t boundaries = p.num_chunks - 1;                         // boundary b lies between chunks b and b + 1
-    const int64_t b0 = ((int64_t)blockIdx.x * kShWaves + wave_in_block) * 64;
+    const int64_t b0 = ((int64_t)blockIdx.x * kCellWaves + wave_in_block) * 64;
     if (b0 >= boundaries) return;
     const int64_t b = b0 + lane;
     const size_t C = p.num_channels;
@@ -243,10 +225,10 @@ __global__ __launch_bounds__(kShBlock) void sh_entries_coeffs_boundaries_kernel(
     int64_t cell = -1;
     bool longer = false;
     if (b < boundaries) {
-        const int64_t left = sh_cell_at(p, (b + 1) * kShChunk - 1);
-        if (left >= 0 && sh_cell_at(p, (b + 1) * kShChunk) == left && !sh_came_in(p, b, left)) {
+        const int64_t left = cell_at(p, (b + 1) * kCellChunk - 1);
+        if (left >= 0 && cell_at(p, (b + 1) * kCellChunk) == left && !came_in(p, b, left)) {
             cell = left;
-            longer = sh_came_in(p, b + 2, left);
+            longer = came_in(p, b + 2, left);
             if (!longer) {                                               // two chunks: this lane alone
                 const double *first = p.partial + ((size_t)b * 2 + 1) * C;
                 const double *second = p.partial + ((size_t)b + 1) * 2 * C;
@@ -267,7 +249,7 @@ __global__ __launch_bounds__(kShBlock) void sh_entries_coeffs_boundaries_kernel(
             double sum = p.partial[((size_t)first_chunk * 2 + 1) * C + c];
             for (int64_t j0 = first_chunk + 1;; j0 += 64) {
                 const int64_t j = j0 + lane;
-                const uint64_t others = ~__builtin_amdgcn_ballot_w64(sh_came_in(p, j, its_cell));
+                const uint64_t others = ~__builtin_amdgcn_ballot_w64(came_in(p, j, its_cell));
                 const int count = others != 0 ? __builtin_ctzll(others) : 64;    // the chunks in front of the first other
                 const double mine = lane < count ? p.partial[(size_t)j * 2 * C + c] : 0.0;
                 for (int i = 0; i < count; ++i)
@@ -415,8 +397,6 @@ using namespace rf;
 
 namespace {
 
-int64_t sh_chunks(int64_t num_entries) { return (num_entries + kShChunk - 1) / kShChunk; }
-
 template <int DEG>
 void sh_launch_forward(const ShForwardParams &p, hipStream_t stream) {
     const int64_t blocks = (p.total + kShBlock - 1) / kShBlock;
@@ -428,9 +408,8 @@ template <int DEG, int FIRST>
 void sh_launch_coeffs(const ShCoeffParams &p, hipStream_t stream) {
     if constexpr (FIRST < sh_dim(DEG)) {
         constexpr int NB = sh_dim(DEG) - FIRST < kShGroup ? sh_dim(DEG) - FIRST : kShGroup;
-        const int64_t blocks = (p.num_chunks + kShWaves - 1) / kShWaves;
-        hipLaunchKernelGGL((sh_entries_coeffs_kernel<DEG, FIRST, NB>), dim3((uint32_t)blocks), dim3(kShBlock), 0,
-                           stream, p);
+        hipLaunchKernelGGL((sh_entries_coeffs_kernel<DEG, FIRST, NB>), dim3((uint32_t)cell_sweep_blocks(p.num_chunks)),
+                           dim3(kCellBlock), 0, stream, p);
         sh_launch_coeffs<DEG, FIRST + NB>(p, stream);
     }
 }
@@ -484,8 +463,8 @@ int rf_sh_entries_forward(uint32_t degree, int64_t num_cells, int64_t num_entrie
 }
 
 size_t rf_sh_entries_workspace_bytes(int64_t num_entries, uint32_t degree) {
-    if (num_entries <= 0 || degree > 3) return 0;
-    return (size_t)sh_chunks(num_entries) * 2 * (size_t)(3 * (degree + 1) * (degree + 1)) * sizeof(double);
+    if (degree > 3) return 0;
+    return cell_workspace_bytes(num_entries, 3 * (degree + 1) * (degree + 1));
 }
 
 int rf_sh_entries_backward_coeffs(uint32_t degree, int64_t num_cells, int64_t num_entries, uint32_t num_rays,
@@ -499,19 +478,13 @@ int rf_sh_entries_backward_coeffs(uint32_t degree, int64_t num_cells, int64_t nu
     if (num_cells < 0) return fail(RF_ERR_INVALID_ARGUMENT, "%s: negative cell count", what);
     if (num_cells == 0) return RF_OK;
     if (!grad_coeffs) return fail(RF_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+    const uint32_t channels = 3 * (degree + 1) * (degree + 1);
     if (num_entries > 0 && num_rays > 0) {
         if (!sorted_cells || !entries || !entry_rays || !directions || !rgb || !grad_rgb)
             return fail(RF_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
-        if (!workspace || workspace_bytes < rf_sh_entries_workspace_bytes(num_entries, degree))
-            return fail(RF_ERR_WORKSPACE, "%s: workspace missing or too small", what);
-        if ((reinterpret_cast<uintptr_t>(workspace) & 7u) != 0)
-            return fail(RF_ERR_WORKSPACE, "%s: the workspace must be 8-byte aligned", what);
-        if (rf_reduce_entries_chunk() != (uint32_t)kShChunk)
-            return fail(RF_ERR_INVALID_ARGUMENT, "%s: built with another chunk than rf_reduce_entries", what);
-        if ((sh_chunks(num_entries) + kShWaves - 1) / kShWaves >= ((int64_t)1 << 31))
-            return fail(RF_ERR_INVALID_ARGUMENT, "%s: too many entries for one launch", what);
+        const int rc = cell_check(what, num_entries, channels, workspace, workspace_bytes);
+        if (rc != RF_OK) return rc;
     }
-    const uint32_t channels = 3 * (degree + 1) * (degree + 1);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (hipMemsetAsync(grad_coeffs, 0, (size_t)num_cells * channels * sizeof(float), s) != hipSuccess)
         return check_launch(what);
@@ -519,7 +492,7 @@ int rf_sh_entries_backward_coeffs(uint32_t degree, int64_t num_cells, int64_t nu
     ShCoeffParams p{};
     p.num_cells = num_cells;
     p.total = num_entries;
-    p.num_chunks = sh_chunks(num_entries);
+    p.num_chunks = cell_chunks(num_entries);
     p.num_rays = num_rays;
     p.num_channels = channels;
     p.sorted_cells = sorted_cells;
@@ -536,15 +509,9 @@ int rf_sh_entries_backward_coeffs(uint32_t degree, int64_t num_cells, int64_t nu
         case 2: sh_launch_coeffs<2, 0>(p, s); break;
         default: sh_launch_coeffs<3, 0>(p, s); break;
     }
-    int rc = check_launch(what);
+    const int rc = check_launch(what);
     if (rc != RF_OK) return rc;
-    if (p.num_chunks > 1) {
-        const int64_t waves = (p.num_chunks - 1 + 63) / 64;
-        hipLaunchKernelGGL(sh_entries_coeffs_boundaries_kernel, dim3((uint32_t)((waves + kShWaves - 1) / kShWaves)),
-                           dim3(kShBlock), 0, s, p);
-        return check_launch(what);
-    }
-    return RF_OK;
+    return cell_launch_boundaries(what, sh_entries_coeffs_boundaries_kernel, p, s);
 }
 
 int rf_sh_entries_backward_directions(uint32_t degree, int64_t num_cells, int64_t num_entries, uint32_t num_rays,

@@ -23,6 +23,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .scene_ops import _ptr, _stream as _stream_ptr
 
 _DEFAULT_WEIGHT_THRESHOLD = 0.001  # default_trace_settings(), src/tracing/pipeline.h:15-20
 _DEFAULT_MAX_INTERSECTIONS = 1024
@@ -52,10 +53,6 @@ def _c10_name(dt) -> str:
         torch.bfloat16: "BFloat16", torch.int32: "Int", torch.int64: "Long",
         torch.uint32: "UInt32", torch.uint8: "Byte", torch.int16: "Short", torch.bool: "Bool",
     }.get(dt, str(dt))
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 #: bumped by invalidate_caches(): every packed-foam / trail / ray-order cache entry made before the
@@ -109,10 +106,6 @@ def _source_key(t, t_c):
         return _tensor_key(t_c)
     k = _tensor_key(t)
     return k if isinstance(k, _Uncacheable) else k + (tuple(t.stride()), int(t.storage_offset()))
-
-
-def _stream_ptr(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class _FoamCache:

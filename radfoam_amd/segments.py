@@ -20,6 +20,9 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib
+from .scene_ops import _ptr, _stream
+
 
 def _check_offsets(offsets):
     if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
@@ -139,8 +142,6 @@ class _CompositeEntries(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sigma, values, t_enter, t_exit, offsets):
-        from . import _lib
-        from .pipeline import _ptr, _stream_ptr
 
         dev = sigma.device
         num_rays, total, channels = offsets.numel() - 1, sigma.size(0), values.size(1)
@@ -156,14 +157,12 @@ class _CompositeEntries(torch.autograd.Function):
         with torch.cuda.device(dev):
             rc = _lib.load().rf_composite_entries_forward(
                 num_rays, _ptr(offsets), total, _ptr(t_enter_c), _ptr(t_exit_c), _ptr(sigma_c), _ptr(values_c),
-                channels, _ptr(out), _stream_ptr(dev))
+                channels, _ptr(out), _stream(dev))
         _lib.check(rc)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        from . import _lib
-        from .pipeline import _ptr, _stream_ptr
 
         sigma, values, t_enter, t_exit, offsets = ctx.saved_tensors
         dev = sigma.device
@@ -176,7 +175,7 @@ class _CompositeEntries(torch.autograd.Function):
             with torch.cuda.device(dev):
                 rc = _lib.load().rf_composite_entries_backward(
                     num_rays, _ptr(offsets), total, _ptr(t_enter), _ptr(t_exit), _ptr(sigma), _ptr(values), channels,
-                    _ptr(grad_out), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _stream_ptr(dev))
+                    _ptr(grad_out), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _stream(dev))
             _lib.check(rc)
         return (grads[0], grads[1], *_times_grads(ctx, grads[2], grads[3]), None)
 
@@ -265,8 +264,6 @@ class _RayDistortion(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sigma, t_enter, t_exit, s_enter, s_exit, offsets):
-        from . import _lib
-        from .pipeline import _ptr, _stream_ptr
 
         dev = sigma.device
         num_rays, total = offsets.numel() - 1, sigma.size(0)
@@ -287,14 +284,12 @@ class _RayDistortion(torch.autograd.Function):
         with torch.cuda.device(dev):
             rc = _lib.load().rf_ray_distortion_forward(
                 num_rays, _ptr(offsets), total, _ptr(t_enter_c), _ptr(t_exit_c), _ptr(sigma_c), _ptr(measure[0]),
-                _ptr(measure[1]), _ptr(out), _stream_ptr(dev))
+                _ptr(measure[1]), _ptr(out), _stream(dev))
         _lib.check(rc)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        from . import _lib
-        from .pipeline import _ptr, _stream_ptr
 
         sigma, t_enter, t_exit, offsets = ctx.saved_tensors[:4]
         measure = ctx.saved_tensors[4:] if ctx.own_measure else (None, None)
@@ -309,7 +304,7 @@ class _RayDistortion(torch.autograd.Function):
                 rc = _lib.load().rf_ray_distortion_backward(
                     num_rays, _ptr(offsets), total, _ptr(t_enter), _ptr(t_exit), _ptr(sigma), _ptr(measure[0]),
                     _ptr(measure[1]), _ptr(grad_out), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]),
-                    _ptr(grads[4]), _stream_ptr(dev))
+                    _ptr(grads[4]), _stream(dev))
             _lib.check(rc)
         return (grads[0], *_times_grads(ctx, grads[1], grads[2]), grads[3], grads[4], None)
 
@@ -417,8 +412,6 @@ class _RayQuantiles(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sigma, t_enter, t_exit, levels, offsets):
-        from . import _lib
-        from .pipeline import _ptr, _stream_ptr
 
         dev = sigma.device
         num_rays, total, num_q = offsets.numel() - 1, sigma.size(0), levels.size(1)
@@ -436,7 +429,7 @@ class _RayQuantiles(torch.autograd.Function):
             with torch.cuda.device(dev):
                 rc = _lib.load().rf_ray_quantiles_forward(
                     num_rays, _ptr(offsets), total, _ptr(t_enter_c), _ptr(t_exit_c), _ptr(sigma_c), num_q,
-                    _ptr(levels), _ptr(depth), _ptr(entries), _stream_ptr(dev))
+                    _ptr(levels), _ptr(depth), _ptr(entries), _stream(dev))
             _lib.check(rc)
         ctx.save_for_backward(sigma_c, t_enter_c, t_exit_c, offsets, levels, entries)
         ctx.mark_non_differentiable(entries)
@@ -444,8 +437,6 @@ class _RayQuantiles(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_depth, _grad_entries):
-        from . import _lib
-        from .pipeline import _ptr, _stream_ptr
 
         sigma, t_enter, t_exit, offsets, levels, entries = ctx.saved_tensors
         dev = sigma.device
@@ -458,7 +449,7 @@ class _RayQuantiles(torch.autograd.Function):
             with torch.cuda.device(dev):
                 rc = _lib.load().rf_ray_quantiles_backward(
                     num_rays, _ptr(offsets), total, _ptr(t_enter), _ptr(t_exit), _ptr(sigma), num_q, _ptr(levels),
-                    _ptr(entries), _ptr(grad_depth), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _stream_ptr(dev))
+                    _ptr(entries), _ptr(grad_depth), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _stream(dev))
             _lib.check(rc)
         return (grads[0], *_times_grads(ctx, grads[1], grads[2]), None, None)
 
@@ -502,9 +493,7 @@ def ray_quantiles(seg, sigma: torch.Tensor, quantiles: torch.Tensor, backend=Non
     num_rays, total, num_q = _check_quantiles_inputs(seg, sigma, quantiles)
     chosen = _choose_backend(backend, sigma, "sigma")
     if chosen == "hip":
-        from . import _lib
-
-        most = int(_lib.load().rf_quantiles_max())
+        most =int(_lib.load().rf_quantiles_max())
         if num_q > most and backend is None:
             chosen = "torch"
         elif num_q > most:
@@ -550,8 +539,6 @@ class _EntryWeights(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sigma, t_enter, t_exit, offsets, with_transmittance):
-        from . import _lib
-        from .pipeline import _ptr, _stream_ptr
 
         dev = sigma.device
         num_rays, total = offsets.numel() - 1, sigma.size(0)
@@ -570,14 +557,12 @@ class _EntryWeights(torch.autograd.Function):
             with torch.cuda.device(dev):
                 rc = _lib.load().rf_entry_weights_forward(
                     num_rays, _ptr(offsets), total, _ptr(t_enter_c), _ptr(t_exit_c), _ptr(sigma_c), _ptr(weights),
-                    _ptr(transmittance), _stream_ptr(dev))
+                    _ptr(transmittance), _stream(dev))
             _lib.check(rc)
         return (weights, transmittance) if with_transmittance else weights
 
     @staticmethod
     def backward(ctx, grad_weights, grad_transmittance=None):
-        from . import _lib
-        from .pipeline import _ptr, _stream_ptr
 
         sigma, t_enter, t_exit, offsets = ctx.saved_tensors
         dev = sigma.device
@@ -592,7 +577,7 @@ class _EntryWeights(torch.autograd.Function):
             with torch.cuda.device(dev):
                 rc = _lib.load().rf_entry_weights_backward(
                     num_rays, _ptr(offsets), total, _ptr(t_enter), _ptr(t_exit), _ptr(sigma), _ptr(g_w), _ptr(g_t),
-                    _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _stream_ptr(dev))
+                    _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _stream(dev))
             _lib.check(rc)
         return (grads[0], *_times_grads(ctx, grads[1], grads[2]), None, None)
 
@@ -766,8 +751,6 @@ def segment_points_grad(seg, exit_cells, points, rays, grad_t_enter, grad_t_exit
 
 def _segment_grad_hip(symbol, out, seg, exit_cells, points, rays, grad_t_enter, grad_t_exit, num_rays, total):
     """The launch both gradient kernels share: ``symbol`` accumulates into the zeroed ``out``."""
-    from . import _lib
-    from .pipeline import _ptr, _stream_ptr
 
     dev = points.device
     if total == 0 or points.size(0) == 0 or num_rays == 0:
@@ -792,7 +775,7 @@ def _segment_grad_hip(symbol, out, seg, exit_cells, points, rays, grad_t_enter, 
         rc = getattr(_lib.load(), symbol)(
             points_c.size(0), _ptr(points_c), num_rays, _ptr(rays_c), _ptr(offsets), total, _ptr(entry_ray),
             _ptr(cells), _ptr(t_enter), _ptr(t_exit), _ptr(exits), _ptr(g_enter), _ptr(g_exit), _ptr(out),
-            _stream_ptr(dev))
+            _stream(dev))
     _lib.check(rc)
     return out
 

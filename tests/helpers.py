@@ -215,3 +215,25 @@ def backward_case(foam_factory, d, seed, image, quantiles, with_error, n_points=
     fwd, ref, k0, k0s = oracle_backward_elements(d, fm, rays, starts, g, q, dg, err)
     return {"d": d, "fm": fm, "rays": rays, "starts": starts, "q": q, "dg": dg, "g": g, "err": err, "fwd": fwd,
             "ref": ref, "k0": k0, "k0_by_tensor": k0s, "settings": {}}
+
+
+def cell_list_lengths(k):
+    """Entries per cell, in cell order, for the kernels that sweep a walk by cell in chunks of k positions.  With K the
+    chunk: 0, 1, 63, 64, 65, K-1, K, K+1 and 2K+130 all occur; cell 7 ends exactly on a chunk boundary and cell 8, of K
+    entries, begins and ends on one; cell 10 begins one position behind a boundary, so the chunk after that lies wholly
+    inside it; cells are empty at both ends and in the middle; the total is no multiple of 64."""
+    lengths = [0, 1, 63, 64, 65, 0, k - 1]
+    lengths.append(k - sum(lengths) % k)                           # cell 7: up to the next boundary
+    assert sum(lengths) % k == 0 and lengths[7] > 0
+    lengths += [k, k + 1, 2 * k + 130, 7, 0, 0]
+    begin = sum(lengths[:10])
+    assert begin % k == 1 and (begin + lengths[10]) // k - begin // k == 2 and sum(lengths) % 64 != 0
+    return lengths
+
+
+def cell_list_lengths_long(k):
+    """cell_list_lengths, then one list of 70 chunks, more than the boundary launch adds in one step, and an empty cell
+    behind it."""
+    lengths = cell_list_lengths(k) + [70 * k + 5, 0]
+    assert sum(lengths) % 64 != 0
+    return lengths

@@ -45,8 +45,9 @@ def test_sources_are_built_but_not_part_of_the_source_hash():
 
     names = lambda paths: {os.path.basename(p) for p in paths}
     assert "rf_cell_reduce.hip" in names(build.EXTRA_SOURCES)
-    assert {"radfoam_hip_cell_reduce.h", "rf_ray_sweep.hpp"} <= names(build.EXTRA_HEADERS)
-    assert not names(build.SOURCES + build.HEADERS) & {"rf_cell_reduce.hip", "radfoam_hip_cell_reduce.h"}
+    assert {"radfoam_hip_cell_reduce.h", "rf_ray_sweep.hpp", "rf_cell_sweep.hpp"} <= names(build.EXTRA_HEADERS)
+    assert not names(build.SOURCES + build.HEADERS) & {"rf_cell_reduce.hip", "radfoam_hip_cell_reduce.h",
+                                                       "rf_cell_sweep.hpp"}
     assert not names(build.SOURCES + build.HEADERS) & names(build.EXTRA_SOURCES + build.EXTRA_HEADERS)
     lib = _lib.load()
     for name in ("rf_reduce_entries", "rf_reduce_entries_chunk", "rf_reduce_entries_workspace_bytes"):

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.helpers import cell_list_lengths as _lengths
 from tests import segments_ref as S
 
 pytestmark = pytest.mark.gpu
@@ -24,20 +25,6 @@ def _chunk():
     k = int(_lib.load().rf_reduce_entries_chunk())
     assert k >= 256 and k % 64 == 0
     return k
-
-
-def _lengths(k):
-    """Entries per cell, in cell order.  With K the chunk: 0, 1, 63, 64, 65, K-1, K, K+1 and 2K+130 all occur; cell 7 ends
-    exactly on a chunk boundary and cell 8, of K entries, begins and ends on one; cell 10 begins one position behind a
-    boundary, so the chunk after that lies wholly inside it; cells are empty at both ends and in the middle; the total
-    is no multiple of 64."""
-    lengths = [0, 1, 63, 64, 65, 0, k - 1]
-    lengths.append(k - sum(lengths) % k)                           # cell 7: up to the next boundary
-    assert sum(lengths) % k == 0 and lengths[7] > 0
-    lengths += [k, k + 1, 2 * k + 130, 7, 0, 0]
-    begin = sum(lengths[:10])
-    assert begin % k == 1 and (begin + lengths[10]) // k - begin // k == 2 and sum(lengths) % 64 != 0
-    return lengths
 
 
 def _index(lengths, seed):

@@ -72,7 +72,8 @@ def test_public_surface_build_lists_and_argument_checks():
     assert radfoam.sh_entries is radfoam_amd.sh_entries is sys.modules["radfoam_amd.sh_entries"].sh_entries
     names = lambda paths: {os.path.basename(p) for p in paths}
     assert "rf_sh_entries.hip" in names(build.EXTRA_SOURCES)
-    assert "radfoam_hip_sh_entries.h" in names(build.EXTRA_HEADERS)
+    assert {"radfoam_hip_sh_entries.h", "rf_cell_sweep.hpp"} <= names(build.EXTRA_HEADERS)
+    assert "rf_cell_sweep.hpp" not in names(build.SOURCES + build.HEADERS)
     assert not names(build.SOURCES + build.HEADERS) & names(build.EXTRA_SOURCES + build.EXTRA_HEADERS)
     assert "rf_math.hpp" in names(build.HEADERS)                   # included, and still part of the source hash
     for path in build.EXTRA_SOURCES + build.EXTRA_HEADERS:
