@@ -15,6 +15,7 @@ from .geometry import (BoxedCellGeometry, BoxedCellMoments, CellGeometry, CellMo
                        differentiable_cell_moments_in_box, face_area_grad, face_area_in_box_grad)
 from .isosurface import IsoMesh, isosurface, isosurface_vertices, isosurface_vertices_grad
 from .locate import FieldSamples, TetLocation, interpolate, interpolate_grad, locate_tets
+from .nearest import CellLocation, locate_cells
 from .mesh import CellMesh, cell_mesh, mesh_vertices, mesh_vertices_grad
 from .pipeline import Pipeline, create_pipeline, invalidate_caches
 from .scene_ops import pack_attributes
@@ -37,5 +38,5 @@ __all__ = [
     "cell_geometry_in_box_grad", "differentiable_cell_geometry_in_box", "BoxedCellMoments", "cell_moments_in_box",
     "cell_moments_in_box_grad", "differentiable_cell_moments_in_box", "face_area_in_box_grad", "IsoMesh", "isosurface",
     "isosurface_vertices", "isosurface_vertices_grad", "DelaunayTets", "delaunay_tets",
-    "TetLocation", "locate_tets", "FieldSamples", "interpolate", "interpolate_grad",
+    "TetLocation", "locate_tets", "FieldSamples", "interpolate", "interpolate_grad", "CellLocation", "locate_cells",
 ]

@@ -68,7 +68,7 @@ class LaunchOpts(C.Structure):
 # radfoam_hip_composite.h, radfoam_hip_distortion.h, radfoam_hip_quantiles.h, radfoam_hip_cell_reduce.h,
 # radfoam_hip_sh_entries.h, radfoam_hip_entry_weights.h, radfoam_hip_face_area_grad.h, radfoam_hip_mesh.h, radfoam_hip_moments.h,
 # radfoam_hip_moments_grad.h, radfoam_hip_box.h, radfoam_hip_box_grad.h, radfoam_hip_box_moments.h, radfoam_hip_box_area_grad.h
-# radfoam_hip_isosurface.h, radfoam_hip_tets.h and radfoam_hip_locate.h declare:
+# radfoam_hip_isosurface.h, radfoam_hip_tets.h, radfoam_hip_locate.h and radfoam_hip_nearest.h declare:
 # name -> (restype, argtypes)
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -188,6 +188,7 @@ SYMBOLS = {
     "rf_locate_walk": (_INT, [_P, _U32, _P, _P, _U32, _U32, _P, _P, _U32, _U32, _P, _P, _P, _P]),
     "rf_interpolate": (_INT, [_P, _U32, _P, _U32, _U32, _P, _U32, _P, _P, _U32, _P, _P, _P, _P]),
     "rf_interpolate_grad": (_INT, [_P, _U32, _P, _U32, _U32, _P, _U32, _P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rf_locate_cells": (_INT, [_P, _U32, _P, _P, _U32, _P, _P, _U32, _U32, _U32, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -28,7 +28,7 @@ EXTRA_SOURCES = [os.path.join(_CSRC, n) for n in ("rf_cell_geometry.hip", "rf_se
                                                       "rf_cell_box_grad.hip", "rf_cell_box_moments.hip",
                                                       "rf_cell_box_moments_grad.hip",
                                                       "rf_cell_box_area_grad.hip", "rf_isosurface.hip", "rf_tets.hip",
-                                                      "rf_locate.hip")]
+                                                      "rf_locate.hip", "rf_nearest.hip")]
 EXTRA_HEADERS = [os.path.join(_CSRC, n) for n in ("rf_clip.hpp", "rf_clip_grad.hpp", "rf_ray_sweep.hpp",
                                                       "rf_segments_face.hpp", "rf_clip_area_grad.hpp",
                                                       "rf_clip_mesh.hpp", "rf_clip_moments.hpp",
@@ -37,7 +37,7 @@ EXTRA_HEADERS = [os.path.join(_CSRC, n) for n in ("rf_clip.hpp", "rf_clip_grad.h
                                                       "rf_clip_box_moments_grad.hpp",
                                                       "rf_clip_box_area_grad.hpp", "rf_cell_wave.hpp",
                                                       "rf_cell_sweep.hpp", "rf_iso.hpp", "rf_tets.hpp",
-                                                      "rf_locate.hpp")] + [
+                                                      "rf_locate.hpp", "rf_nearest.hpp")] + [
     os.path.join(os.path.dirname(_HERE), "include", n) for n in ("radfoam_hip_geometry.h", "radfoam_hip_segments.h",
                                                                "radfoam_hip_composite.h",
                                                                "radfoam_hip_geometry_grad.h",
@@ -57,7 +57,8 @@ EXTRA_HEADERS = [os.path.join(_CSRC, n) for n in ("rf_clip.hpp", "rf_clip_grad.h
                                                                "radfoam_hip_box_area_grad.h",
                                                                "radfoam_hip_isosurface.h",
                                                                "radfoam_hip_tets.h",
-                                                               "radfoam_hip_locate.h")]
+                                                               "radfoam_hip_locate.h",
+                                                               "radfoam_hip_nearest.h")]
 OBJ_DIR = os.path.join(_CSRC, "_obj")
 OUTPUT = os.path.join(_HERE, "libradfoam_hip.so")
 

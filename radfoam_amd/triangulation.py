@@ -213,19 +213,35 @@ class Triangulation:
     def vert_to_tet(self):
         return self._mesh().vert_to_tet
 
-    def locate(self, queries: torch.Tensor):
+    def locate_cells(self, queries: torch.Tensor, start=None):
+        """CellLocation(cell int64[...], hops int32[...]) of float32 CUDA ``queries`` [...,3] (radfoam.locate_cells): the
+        site of the object's (kd-ordered) points nearest to every query, by the greedy walk over its own neighbour lists,
+        seeded from 1024 strided sites or started at ``start``."""
+        from .nearest import locate_cells
+        return locate_cells(self._points, self._adjacency, self._offsets, queries, start=start)
+
+    def locate(self, queries: torch.Tensor, nearest: str = "tree"):
         """TetLocation(tet int64[...], hops int32[...]) of float32 CUDA ``queries`` [...,3] in ``tets()``
-        (radfoam.locate_tets): every walk starts at ``vert_to_tet()`` of the site nearest to its query, found through the
-        AABB tree of the kd-ordered points (nearest_point_tree).  The tree is built on the first call and kept, with the
-        tetrahedra, until the next rebuild."""
+        (radfoam.locate_tets): every walk starts at ``vert_to_tet()`` of the site nearest to its query.  ``nearest`` says
+        how that site is found: "tree" (the default) through the AABB tree of the kd-ordered points (nearest_point_tree),
+        built on the first call and kept, with the tetrahedra, until the next rebuild; "walk" by ``locate_cells`` over the
+        neighbour lists, without the tree.  The two may start a query that has several nearest sites, or whose nearest
+        sites differ in float32 only, at different tetrahedra: the located tetrahedron differs only for queries on a shared
+        face, edge or vertex, ``hops`` may differ anywhere."""
         from .locate import locate_tets
-        from .scene_ops import nearest_point_tree
+        if nearest not in ("tree", "walk"):
+            raise ValueError("nearest must be 'tree' or 'walk'")
         mesh = self._mesh(adjacency=True)
+        if nearest == "walk":
+            site = self.locate_cells(queries).cell.clamp(0, self._n - 1)   # a query that is not finite: any start will do
+            return locate_tets(self._points, mesh.tets, mesh.tet_adjacency, queries,
+                               start=mesh.vert_to_tet.view(torch.int32)[site])
+        from .scene_ops import nearest_point_tree
         if self._tree is None:
             self._tree = build_aabb_tree(self._points)
         q = queries.detach()
         finite = torch.isfinite(q).all(-1, keepdim=True)               # such a query is not walked: any start will do
-        nearest = nearest_point_tree(self._points, self._tree, torch.where(finite, q, torch.zeros_like(q)))
-        nearest = nearest.view(torch.int32).to(torch.int64).clamp(0, self._n - 1)
-        start = mesh.vert_to_tet.view(torch.int32)[nearest]
+        site = nearest_point_tree(self._points, self._tree, torch.where(finite, q, torch.zeros_like(q)))
+        site = site.view(torch.int32).to(torch.int64).clamp(0, self._n - 1)
+        start = mesh.vert_to_tet.view(torch.int32)[site]
         return locate_tets(self._points, mesh.tets, mesh.tet_adjacency, queries, start=start)
